@@ -7,8 +7,18 @@ RCCL all-reduce of the trainable gradients overlapped with backward).
     python bench.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events around every launch of the dominant kernel
-inside the timed region; `cpu_baseline` times the CPU oracle (port of the reference algorithm) on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps and reports them; everything else it can measure
+is behind `--full`: `roofline` / `kernel_breakdown` (HIP events around every launch of the GEMM / attention / conv kernels in extra
+eager steps after the timed ones), `cpu_baseline` (the CPU oracle, a port of the reference algorithm, on a bounded sample), the
+`comm` record of N > 1 / forced-reducer runs and the committed A/B factor of the last round.
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
+
+`--dump-outputs DIR`: after the timed steps, the timed step (same captured graph) runs once more on the seeded initial state, and
+what it handed back (its loss, and a fixed seeded sample of the trainable parameters it updated and of their gradients) is written
+as DIR/<name>.npy, so two builds can be compared output for output on identical inputs (replay_from_seeded_state says why not the
+K-th timed step itself).
 """
 import argparse
 import json
@@ -55,8 +65,13 @@ def parse():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--graph", default=os.environ.get("DINOUNET_BENCH_GRAPH", "auto"), choices=["auto", "on", "off"],
                     help="capture the train step into a hipGraph (auto = on)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline / kernel breakdown, CPU baseline, comm record")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the profiled eager steps of the roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more on the seeded initial state and write its outputs (loss, "
+                         "sampled parameters and gradients) as DIR/<name>.npy")
     ap.add_argument("--torch-sgd", action="store_true", help="torch clip_grad_norm_ + torch.optim.SGD instead of the fused HIP clip+SGD (same arithmetic)")
     return ap.parse_args()
 
@@ -90,6 +105,9 @@ def main():
         from dinounet_amd.optim import FusedClipSGD                                                # same update + clip 12 (TRN:922), csrc/optim.hip
         opt = FusedClipSGD(params, lr=1e-3, momentum=0.99, nesterov=True, weight_decay=3e-5, max_norm=12.0)
 
+    # --dump-outputs: the seeded state (parameters and buffers as initialised) the dumped step starts from, see replay_from_seeded_state
+    seeded = [t.detach().clone() for t in (*params, *net.buffers())] if a.dump_outputs else None
+
     g = torch.Generator(device="cpu").manual_seed(100 + rank)
     x = torch.randn(a.batch, 3, a.size, a.size, generator=g).to(dev)
     tgt = torch.randint(0, 2, (a.batch, 1, a.size, a.size), generator=g).to(dev)
@@ -115,9 +133,14 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     graph_used = ts.graph is not None          # False when capture was off or fell back to eager steps
-    # roofline leg: the same step run eagerly with a HIP-event pair around every launch of the GEMM / attention kernels
+    final_loss = float(loss.item())            # read now: a captured step returns the same static tensor on every replay
+    if a.dump_outputs:                         # every rank replays (the step may hold collectives), rank 0 writes
+        out_loss = replay_from_seeded_state(ts, net, opt, params, seeded)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, out_loss, params)
+    # roofline leg (--full): the same step run eagerly with a HIP-event pair around every launch of the GEMM / attention kernels
     prof = None
-    if not a.no_roofline or reducer is not None:
+    if a.full and (not a.no_roofline or reducer is not None):
         # every rank runs these eager steps (they contain the gradient / SyncBN / Dice collectives); only rank 0 times its launches.
         # With a reducer they run even under --no-roofline: the `comm` record (exposed all-reduce time, bucket timeline) comes from them
         ts.use_graph = False
@@ -138,7 +161,7 @@ def main():
     prof = ops.PROFILE
     ops.PROFILE = None
     comm = None
-    if reducer is not None:
+    if a.full and reducer is not None:
         # what the N > 1 runs exchange per step and how much of it is exposed: bucket sizes, collective count, the time the (eager)
         # step spends in reducer.finish() after backward = all-reduce time NOT hidden behind the backward pass + the bucket divides, and
         # per bucket (last eager step) when its gradients were gathered, when its all-reduce started and ended, in ms from the step's start
@@ -174,13 +197,12 @@ def main():
         reducer.timeline = None
     if world > 1:
         t = torch.tensor([dt], device=dev)
-        every = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(every, t)
-        per_rank_ms = [round(float(v.item()) / a.steps * 1e3, 3) for v in every]      # spread of the ranks' own clocks around the same K steps
+        if comm is not None:
+            every = [torch.zeros_like(t) for _ in range(world)]
+            dist.all_gather(every, t)
+            comm["ms_per_step_by_rank"] = [round(float(v.item()) / a.steps * 1e3, 3) for v in every]   # spread of the ranks' own clocks around the same K steps
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        if comm is not None:
-            comm["ms_per_step_by_rank"] = per_rank_ms
     ms = dt / a.steps * 1e3
     value = a.batch * world / (dt / a.steps)
 
@@ -192,16 +214,15 @@ def main():
            "config": {"workload": f"{a.model} train step (fwd+loss+bwd+clip+SGD), {a.size}x{a.size}x3 slices, batch {a.batch}/GPU, "
                                   f"frozen ViT + adapter + FAPM + U-Net decoder, random-init weights",
                       "global_batch": a.batch * world, "parallelism": f"dp{world}"},
-           "final_loss": round(float(loss.item()), 5), "hipgraph": bool(graph_used)}
+           "final_loss": round(final_loss, 5), "hipgraph": bool(graph_used)}
     if comm is not None:
         out["comm"] = comm
     # the only trustworthy round-over-round delta is an interleaved same-box A/B of the two trees (box-to-box spread of one tree: ~15 %);
     # its factor is committed beside the raw runs and quoted here so it need not be dug out
-    try:
-        ab = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "ab_vs_prev_round.json")))
+    ab_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "ab_vs_prev_round.json")
+    if a.full and os.path.exists(ab_path):
+        ab = json.load(open(ab_path))
         out["ab_vs_prev_round"], out["ab_source"] = ab["factor"], ab["source"]
-    except Exception:  # noqa: BLE001
-        pass
     if rank == 0:
         if prof is not None:
             try:
@@ -218,7 +239,7 @@ def main():
                 pmc_cycles(r)
             except Exception as e:  # noqa: BLE001
                 out["roofline"] = {"error": repr(e)}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(net, a)
             except Exception as e:  # noqa: BLE001
@@ -239,6 +260,45 @@ def main():
         del reducer
         torch.cuda.synchronize()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 22     # elements per sampled array: 16 MB in fp32
+
+
+def replay_from_seeded_state(ts, net, opt, params, seeded):
+    """The timed step (the same captured graph, or the same eager step with --graph off) run once more after the timed loop, on the
+    seeded state: parameters and buffers as initialised, momentum buffers zero (the optimizer state of a first step); the device RNG is
+    not reset, its offset after W + K steps is the same every run.  Why not simply the K-th timed step: the weight-gradient reductions
+    use fp32 atomics, so a step's gradients vary run to run in the last bits, and training on them amplifies that (bf16 casts of the
+    updated weights round differently): from the third step on, two runs' losses and gradients differ well beyond rounding.  On the
+    seeded state the inputs of the step are identical every run, and so are its outputs up to that rounding."""
+    from dinounet_amd import ops
+    with torch.no_grad():
+        for t, t0 in zip((*params, *net.buffers()), seeded):
+            t.copy_(t0)
+        for st in opt.state.values():
+            if st.get("momentum_buffer") is not None:
+                st["momentum_buffer"].zero_()
+    ops.PACK.invalidate()                      # packed weight copies (the forward refreshes them) are stale
+    loss = ts()
+    torch.cuda.synchronize()
+    return float(loss.item())
+
+
+def dump_outputs(d, loss, params):
+    """What the step of replay_from_seeded_state handed back to its caller, as .npy files (under 40 MB in all): the loss (float64), and
+    the trainable parameters it updated and their gradients (float32), each flattened and concatenated in parameter order -- in full up
+    to DUMP_SAMPLE elements, else the same fixed seeded DUMP_SAMPLE-element subset for both."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+    if flat_p.numel() > DUMP_SAMPLE:
+        idx = torch.randperm(flat_p.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    np.save(os.path.join(d, "loss.npy"), np.array([float(loss)], dtype=np.float64))
+    np.save(os.path.join(d, "params.npy"), flat_p.cpu().numpy())
+    np.save(os.path.join(d, "grads.npy"), flat_g.cpu().numpy())
 
 
 def north_star_targets(prof, steps=1):

@@ -133,7 +133,7 @@ def test_single_rank_rccl_reducer_inside_the_captured_step_bench():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = [sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--no-roofline"]
+    args = [sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "4", "--full", "--no-cpu-baseline", "--no-roofline"]
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
 
     def run(extra):

@@ -13,12 +13,12 @@ for l in sys.stdin:
 echo "# plain single-GPU step (no process group)"
 env -u RANK -u DINOUNET_FORCE_REDUCER python bench.py --steps $S --warmup 5 --no-cpu-baseline --no-roofline 2>/dev/null | python -c "$pick"
 echo "# reducer only (round-5 configuration: gradient buckets, no small collectives)"
-MASTER_PORT=29611 python bench.py --steps $S --warmup 5 --no-cpu-baseline --no-roofline 2>/dev/null | python -c "$pick"
+MASTER_PORT=29611 python bench.py --steps $S --warmup 5 --full --no-cpu-baseline --no-roofline 2>/dev/null | python -c "$pick"
 echo "# + every SyncBN / Dice collective: whole-step capture"
-MASTER_PORT=29612 DINOUNET_FORCE_SMALL_COLLECTIVES=1 python bench.py --steps $S --warmup 5 --no-cpu-baseline --no-roofline 2>/dev/null | python -c "$pick"
+MASTER_PORT=29612 DINOUNET_FORCE_SMALL_COLLECTIVES=1 python bench.py --steps $S --warmup 5 --full --no-cpu-baseline --no-roofline 2>/dev/null | python -c "$pick"
 echo "# + every SyncBN / Dice collective: segmented capture (DINOUNET_COMM_OUTSIDE_GRAPH=1)"
-MASTER_PORT=29613 DINOUNET_FORCE_SMALL_COLLECTIVES=1 DINOUNET_COMM_OUTSIDE_GRAPH=1 python bench.py --steps $S --warmup 5 --no-cpu-baseline --no-roofline 2>/dev/null | python -c "$pick"
+MASTER_PORT=29613 DINOUNET_FORCE_SMALL_COLLECTIVES=1 DINOUNET_COMM_OUTSIDE_GRAPH=1 python bench.py --steps $S --warmup 5 --full --no-cpu-baseline --no-roofline 2>/dev/null | python -c "$pick"
 echo "# + every SyncBN / Dice collective: eager steps (--graph off)"
-MASTER_PORT=29614 DINOUNET_FORCE_SMALL_COLLECTIVES=1 python bench.py --steps $S --warmup 5 --no-cpu-baseline --no-roofline --graph off 2>/dev/null | python -c "$pick"
+MASTER_PORT=29614 DINOUNET_FORCE_SMALL_COLLECTIVES=1 python bench.py --steps $S --warmup 5 --full --no-cpu-baseline --no-roofline --graph off 2>/dev/null | python -c "$pick"
 echo "# soak: the forced whole-step capture, 10 consecutive processes (rc of each)"
-for i in 1 2 3 4 5 6 7 8 9 10; do MASTER_PORT=$((29620+i)) DINOUNET_FORCE_SMALL_COLLECTIVES=1 python bench.py --steps 6 --warmup 4 --no-cpu-baseline --no-roofline >/dev/null 2>&1; echo -n "rc=$? "; done; echo
+for i in 1 2 3 4 5 6 7 8 9 10; do MASTER_PORT=$((29620+i)) DINOUNET_FORCE_SMALL_COLLECTIVES=1 python bench.py --steps 6 --warmup 4 --full --no-cpu-baseline --no-roofline >/dev/null 2>&1; echo -n "rc=$? "; done; echo

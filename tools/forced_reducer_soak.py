@@ -25,7 +25,7 @@ for i in range(n):
     if outside:
         env["DINOUNET_COMM_OUTSIDE_GRAPH"] = "1"
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-roofline", *extra], env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-roofline", *extra], env=env, capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     ok = r.returncode == 0 and line and json.loads(line[-1]).get("hipgraph") and json.loads(line[-1])["comm"]["exposed_after_backward_ms"] is not None
     ok = ok and json.loads(line[-1])["comm"]["capture"].startswith("segments" if outside else "whole_step")
