@@ -87,7 +87,8 @@ class _WindowForward:
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        from . import ops
+        with ops.capture(self.graph):               # (the capture stream's du_gemm scratch exists before the capture: the ViT's K-sliced units run in the graph)
             y = net(self.x)
             self.y = (y[0] if isinstance(y, (list, tuple)) else y).float().contiguous()
 

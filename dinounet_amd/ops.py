@@ -187,19 +187,47 @@ ROUTES = []                  # (a_mode, b_mode, route) of every product since TR
 _KS_PAIRS = _ab_env("DINOUNET_KS_PAIRS", "1") == "1"      # lend du_gemm the pair-exchange scratch (the library decides: du_set_option key 16)
 _KS_SCRATCH = {}
 _KS_RETIRED = []
+_KS_NEED = 4 << 20           # largest ks_ws a product has asked for so far (eager warm-up steps settle it before a capture)
 
 
-def _ks_scratch(nbytes):
-    """du_gemm_args.ks_ws: per (device, stream), persistent; the state words at its head are zeroed once (every launch leaves them zero)"""
-    key = (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
+def _ks_scratch(nbytes, stream=None):
+    """du_gemm_args.ks_ws: per (device, stream), persistent; the state words at its head are zeroed once (every launch leaves them zero).
+    Never created while the stream is capturing: the zeroing would only be a node of that graph, and if the capture is discarded before a
+    replay it never runs while the buffer stays cached under its key -- later launches would read undefined tickets.  Under capture a
+    missing (or too small) buffer is refused: None, and du_gemm runs the product without ks_ws (one unit per column block, one workgroup
+    per tile: the same bits).  ks_scratch_prepare() creates it before the capture begins."""
+    global _KS_NEED
+    _KS_NEED = max(_KS_NEED, nbytes)
+    st = torch.cuda.current_stream() if stream is None else stream
+    key = (st.device.index, st.cuda_stream)
     buf = _KS_SCRATCH.get(key)
     if buf is None or buf.numel() < nbytes:
+        if torch.cuda.is_current_stream_capturing():
+            return None
         if buf is not None:
             _KS_RETIRED.append(buf)      # a captured graph may still hold its address: never handed back to the allocator
-        buf = torch.empty(max(nbytes, 4 << 20), dtype=torch.uint8, device=torch.device("cuda", key[0]))
+        buf = torch.empty(_KS_NEED, dtype=torch.uint8, device=torch.device("cuda", key[0]))
         buf[:131072].zero_()
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()      # zeroed here, used on `stream`: complete before that stream's first launch
         _KS_SCRATCH[key] = buf
     return buf
+
+
+def ks_scratch_prepare(stream):
+    """create (and zero) the ks_ws of `stream` now, eagerly, sized for the largest request seen so far: call it before a capture on that
+    stream begins (ops.capture and training.TrainStep do), so that the K-sliced units / K-split pairs run inside the graph too"""
+    assert not torch.cuda.is_current_stream_capturing()
+    return _ks_scratch(_KS_NEED, stream)
+
+
+def capture(graph, **kw):
+    """torch.cuda.graph(graph, **kw) with du_gemm's in-launch scratch of the capture stream created first (ks_scratch_prepare): the way
+    every capture of product code begins -- a capture begun without it is correct too, but runs its K-sliced units / K-split pairs as
+    one unit per column block / one workgroup per tile"""
+    ctx = torch.cuda.graph(graph, **kw)
+    ks_scratch_prepare(ctx.capture_stream)
+    return ctx
 
 
 def gemm_raw(*, dtype, out_dtype, a_mode, b_mode, M, N, K, A, lda, B, ldb, Cmat, ldc, batch=1, abs_=0, bbs=0, cbs=0,
@@ -239,7 +267,9 @@ def gemm_raw(*, dtype, out_dtype, a_mode, b_mode, M, N, K, A, lda, B, ldb, Cmat,
             out_dtype == DU_F32 or 0 < M % 256 <= 64):
         n_ks = int(_lib.lib().du_gemm_ks_ws_bytes(C.byref(a)))
         if n_ks > 0:
-            a.ks_ws, a.ks_ws_bytes = _ks_scratch(n_ks).data_ptr(), n_ks
+            ks = _ks_scratch(n_ks)
+            if ks is not None:
+                a.ks_ws, a.ks_ws_bytes = ks.data_ptr(), n_ks
     global LAST_GEMM_ROUTE
     if TRACK_ROUTE:
         LAST_GEMM_ROUTE = int(_lib.lib().du_gemm_route(C.byref(a)))

@@ -209,6 +209,7 @@ class TrainStep:
         s.wait_stream(torch.cuda.current_stream())
         self._segments, ops.CAPTURE_CUT, self.reducer.defer = seg, seg.cut, True
         try:
+            ops.ks_scratch_prepare(s)          # du_gemm's in-launch scratch of the capture stream: created and zeroed outside any capture
             with torch.cuda.stream(s):
                 seg.begin()
                 self.loss = self._step()
@@ -255,7 +256,10 @@ class TrainStep:
             if not self.comm_outside_graph:
                 try:
                     graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, capture_error_mode=mode):
+                    # (ops.capture: du_gemm's in-launch scratch of the capture stream is created and zeroed BEFORE the capture -- made inside
+                    #  it, the zeroing would be a graph node that never runs if this capture is discarded)
+                    from . import ops
+                    with ops.capture(graph, capture_error_mode=mode):
                         self.loss = self._step()
                     self.graph = graph
                     self.capture_mode = "whole_step"

@@ -71,7 +71,7 @@ def main():
             L.du_set_option(13, mode)
             fn(); torch.cuda.synchronize()
             gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
+            with ops.capture(gr):
                 for _ in range(5):
                     fn()
             graphs[tag] = gr

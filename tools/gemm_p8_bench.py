@@ -182,7 +182,7 @@ def time_variants(rounds):
             call()
             torch.cuda.synchronize()
             g_ = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_):
+            with ops.capture(g_):
                 for _ in range(10):
                     call()
             graphs[n] = g_

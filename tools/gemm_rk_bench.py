@@ -88,7 +88,7 @@ def main():
             fn()
             torch.cuda.synchronize()
             gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
+            with ops.capture(gr):
                 for _ in range(5):
                     fn()
             graphs[tag] = gr

@@ -35,7 +35,7 @@ def main(rounds):
             ops.mm_wgrad(dy, x)
             torch.cuda.synchronize()
             gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
+            with ops.capture(gr):
                 for _ in range(10):
                     ops.mm_wgrad(dy, x)
             graphs[n] = gr

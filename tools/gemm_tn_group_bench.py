@@ -42,7 +42,7 @@ def main(rounds):
             run(grp)
             torch.cuda.synchronize()
             gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
+            with ops.capture(gr):
                 run(grp)
             graphs[tag] = gr
         ts = {k: [] for k in graphs}

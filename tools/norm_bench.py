@@ -18,7 +18,7 @@ bf = torch.bfloat16
 def timeit(fn, rounds):
     fn(); torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    with ops.capture(g):
         for _ in range(5):
             fn()
     ts = []

@@ -27,7 +27,7 @@ res = {}
 for name, fn in (("heads+inplace", heads), ("rope in drain", drain), ("unfused", unfused)):
     fn(); torch.cuda.synchronize()
     gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
+    with ops.capture(gr):
         for _ in range(10): fn()
     res[name] = gr
 for _ in range(3):

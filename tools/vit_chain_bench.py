@@ -34,7 +34,7 @@ def chains(a):
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with ops.capture(g):
             out = vit.get_intermediate_layers(x, n=taps, dtype=torch.bfloat16)
         graphs[nc] = (g, out)
     ref = [t[0].float().clone() for t in graphs[a.chains[0]][1]]
@@ -85,7 +85,7 @@ def fills(a):
             ops.mm(x, w, out=out)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with ops.capture(g):
                 for _ in range(10):
                     ops.mm(x, w, out=out)
             ops_[fill] = (g, x, w, out)

@@ -58,7 +58,7 @@ def main(rounds):
     def capture(fn):
         fn(); torch.cuda.synchronize()
         gr = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr):
+        with ops.capture(gr):
             fn()
         return gr
 
