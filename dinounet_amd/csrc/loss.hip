@@ -173,3 +173,448 @@ extern "C" int du_dice_ce_bwd(const float* logits, const int64_t* target, const 
 #undef CALL
   return du_check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The other two label configurations of the reference trainer (nnUNetTrainer._build_loss, nnUNetTrainer.py:355-365):
+//  * ignore label (sparse annotation): DC_and_CE_loss(ignore_label) (compound_losses.py:31-56, dice.py:72-119 with loss_mask):
+//      m = [t != ignore];  CE = sum m (-log p_t) / n_valid, exactly 0 when n_valid = 0 (compound_losses.py:52-53, decided on the device);
+//      Dice over classes 1..K-1 with p and the one-hot target multiplied by m.
+//  * regions (sigmoid outputs, overlapping classes): DC_and_BCE_loss (compound_losses.py:83-99), MemoryEfficientSoftDiceLoss(sigmoid,
+//      do_bg=True); target = uint8 one-hot planes (B, R + u, HW), u = 1 with an ignore label, m = 1 - target[:, R]:
+//      BCE = sum m bce / clip(n_valid, 1e-8) with n_valid counted in PIXELS (the (B,1,H,W) mask broadcast over R, :95), else the mean
+//      over all B R HW elements; Dice over all R regions on sigmoid(x).
+// Sums layouts: masked softmax [CE_sum, n_valid, (I_c, P_c, G_c) c = 1..K-1], regions [BCE_sum, n_valid, (I_r, P_r, G_r) r = 0..R-1]:
+// under data parallelism only sums[2:] are all-reduced.  `finish` also writes the CE / BCE scale (1/n_valid or 0) after the 2(K-1) /
+// 2R dice coefficients, so the backward pass needs no host value.  Each lane handles 4 consecutive pixels of one image (16 B per fp32
+// logits plane, one dword per uint8 plane, 32 B of int64 labels); when HW % 4 != 0 the rows are not 16 B aligned and every quad takes
+// the guarded scalar path (the last quad of an image is partial).  Reductions are two-stage, per-block partial rows + one block adding
+// them (partial_rows_sum_kernel): no float atomics, bit-reproducible across calls and graph replays.
+namespace {
+
+constexpr int MAXR = 8;
+
+__device__ __forceinline__ void ld4f(const float* __restrict__ p, bool vec, int n, float o[4]) {
+  if (vec) {
+    const float4 v = *reinterpret_cast<const float4*>(p);
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = j < n ? p[j] : 0.f;
+  }
+}
+__device__ __forceinline__ void st4f(float* __restrict__ p, bool vec, int n, const float o[4]) {
+  if (vec) {
+    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++) if (j < n) p[j] = o[j];
+  }
+}
+__device__ __forceinline__ void ld4l(const int64_t* __restrict__ p, bool vec, int n, int64_t fill, int64_t o[4]) {
+  if (vec) {
+    const longlong2 a = reinterpret_cast<const longlong2*>(p)[0], b = reinterpret_cast<const longlong2*>(p)[1];
+    o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = j < n ? p[j] : fill;
+  }
+}
+// 4 uint8 of one plane in one dword (byte j = pixel j)
+__device__ __forceinline__ uint32_t ld4b(const uint8_t* __restrict__ p, bool vec, int n) {
+  if (vec) return *reinterpret_cast<const uint32_t*>(p);
+  uint32_t w = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) if (j < n) w |= (uint32_t)p[j] << (8 * j);
+  return w;
+}
+__device__ __forceinline__ void st4b(uint8_t* __restrict__ p, bool vec, int n, uint32_t w) {
+  if (vec) {
+    *reinterpret_cast<uint32_t*>(p) = w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++) if (j < n) p[j] = (uint8_t)(w >> (8 * j));
+  }
+}
+
+template <int NS>
+__device__ __forceinline__ void block_partial_store(float (&acc)[NS], float* __restrict__ part) {
+  __shared__ float red[4][NS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < NS; i++) {
+    const float s = wave_sum(acc[i]);
+    if (lane == 0) red[wave][i] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NS) part[(long)blockIdx.x * NS + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// second stage of the new sums passes: ONE block adds the per-block partial rows (blocks x NS).  Every thread loads all NS columns of its
+// rows at once, so the block waits for one memory round trip instead of NS dependent ones (dice_ce_sum_kernel above walks the columns one
+// at a time, with a strided load and an eight-barrier tree each: ~2 us per column, two thirds of a 512^2 batch-8 sums pass).  Fixed order
+// (rows t, t + 256, ... per thread, DPP wave tree, waves 0..3): bit-reproducible.
+template <int NS>
+__global__ __launch_bounds__(256) void partial_rows_sum_kernel(const float* __restrict__ part, float* __restrict__ sums, int blocks) {
+  float acc[NS];
+#pragma unroll
+  for (int i = 0; i < NS; i++) acc[i] = 0.f;
+  for (int b = threadIdx.x; b < blocks; b += 256) {
+    const float* row = part + (long)b * NS;
+#pragma unroll
+    for (int i = 0; i < NS; i++) acc[i] += row[i];
+  }
+  block_partial_store<NS>(acc, sums);     // gridDim.x == 1: row 0 of `sums`
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                                                     float* __restrict__ part, int B, long HW, int64_t ignore, bool vec) {
+  constexpr int NS = 2 + 3 * (K - 1);
+  float acc[NS];
+#pragma unroll
+  for (int i = 0; i < NS; i++) acc[i] = 0.f;
+  const long nq = (HW + 3) >> 2, items = (long)B * nq;
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
+    const long b = it / nq, r0 = (it - b * nq) * 4;
+    const int n = vec ? 4 : (int)min(4L, HW - r0);
+    const float* lp = logits + b * K * HW + r0;
+    float v[K][4];
+#pragma unroll
+    for (int k = 0; k < K; k++) ld4f(lp + (long)k * HW, vec, n, v[k]);
+    int64_t t[4];
+    ld4l(target + b * HW + r0, vec, n, ignore, t);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const bool valid = t[j] != ignore;
+      float mx = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < K; k++) mx = fmaxf(mx, v[k][j]);
+      float e[K], se = 0.f, xt = mx;
+#pragma unroll
+      for (int k = 0; k < K; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
+      const float inv = 1.f / se;
+      acc[0] += valid ? (mx + __logf(se)) - xt : 0.f;     // -log p_t = logsumexp - x_t
+      acc[1] += valid ? 1.f : 0.f;
+#pragma unroll
+      for (int k = 1; k < K; k++) {
+        const float pk = e[k] * inv;
+        const bool hit = valid && k == t[j];
+        acc[2 + 3 * (k - 1)] += hit ? pk : 0.f;
+        acc[2 + 3 * (k - 1) + 1] += valid ? pk : 0.f;
+        acc[2 + 3 * (k - 1) + 2] += hit ? 1.f : 0.f;
+      }
+    }
+  }
+  block_partial_store<NS>(acc, part);
+}
+
+// per-class dice coefficients shared by both configurations: loss -= mean_c dc_c; d loss / d q_c(pixel) = m (ca_c y_c + cb_c), q = the
+// probability the dice terms see.  dc_c is summed before the division so an all-ignored batch gives exactly 1 (s / s) per class.
+__device__ float dice_coefs(const float* __restrict__ s3, float* __restrict__ coef, int C, float smooth, float grad_mult) {
+  float dc_sum = 0.f;
+  const float invc = 1.f / (float)C;
+  for (int c = 0; c < C; c++) {
+    const float I = s3[3 * c], P = s3[3 * c + 1], G = s3[3 * c + 2];
+    const float num = 2.f * I + smooth;
+    const float raw = G + P + smooth;
+    const float den = fmaxf(raw, 1e-8f);
+    dc_sum += num / den;
+    coef[2 * c] = -2.f * invc / den * grad_mult;
+    coef[2 * c + 1] = (raw > 1e-8f ? num / (den * den) * invc : 0.f) * grad_mult;
+  }
+  return dc_sum / (float)C;
+}
+
+// coef = [(ca_c, cb_c) c = 1..K-1, ce_scale]
+__global__ void dice_ce_masked_coef_kernel(const float* __restrict__ sums, float* __restrict__ loss, float* __restrict__ coef, int K,
+                                           float smooth, float grad_mult) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float dc = dice_coefs(sums + 2, coef, K - 1, smooth, grad_mult);
+  const float nv = sums[1];
+  const float ce_scale = nv > 0.f ? 1.f / nv : 0.f;
+  coef[2 * (K - 1)] = ce_scale;
+  loss[0] = sums[0] * ce_scale - dc;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void dice_ce_masked_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                                                 const float* __restrict__ coef, const float* __restrict__ gout,
+                                                                 float* __restrict__ dlogits, int B, long HW, int64_t ignore, bool vec) {
+  float ca[K], cb[K];
+  ca[0] = 0.f; cb[0] = 0.f;
+#pragma unroll
+  for (int c = 1; c < K; c++) { ca[c] = coef[2 * (c - 1)]; cb[c] = coef[2 * (c - 1) + 1]; }
+  const float ce_scale = coef[2 * (K - 1)];
+  const float go = gout ? gout[0] : 1.f;
+  const long nq = (HW + 3) >> 2, items = (long)B * nq;
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
+    const long b = it / nq, r0 = (it - b * nq) * 4;
+    const int n = vec ? 4 : (int)min(4L, HW - r0);
+    const float* lp = logits + b * K * HW + r0;
+    float v[K][4];
+#pragma unroll
+    for (int k = 0; k < K; k++) ld4f(lp + (long)k * HW, vec, n, v[k]);
+    int64_t t[4];
+    ld4l(target + b * HW + r0, vec, n, ignore, t);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const bool valid = t[j] != ignore;
+      float mx = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < K; k++) mx = fmaxf(mx, v[k][j]);
+      float se = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; k++) { v[k][j] = __expf(v[k][j] - mx); se += v[k][j]; }
+      const float inv = 1.f / se;
+      float g[K], dot = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+        v[k][j] *= inv;
+        g[k] = (k == t[j] ? ca[k] : 0.f) + cb[k];
+        dot += g[k] * v[k][j];
+      }
+#pragma unroll
+      for (int k = 0; k < K; k++)
+        v[k][j] = valid ? go * ((v[k][j] - (k == t[j] ? 1.f : 0.f)) * ce_scale + v[k][j] * (g[k] - dot)) : 0.f;
+    }
+    float* dp = dlogits + b * K * HW + r0;
+#pragma unroll
+    for (int k = 0; k < K; k++) st4f(dp + (long)k * HW, vec, n, v[k]);
+  }
+}
+
+// sigmoid and the stable BCE-with-logits from one exponential: e = exp(-|x|), bce = max(x, 0) - x y + log(1 + e).  The reciprocal is
+// v_rcp_f32 (1 ulp; 1 + e lies in [1, 2]): an IEEE division is a ~10-instruction sequence per element, and at R elements per pixel it
+// made the region kernels VALU-bound
+__device__ __forceinline__ void sigmoid_bce(float x, float y, float& s, float& bce) {
+  const float e = __expf(-fabsf(x));
+  const float inv = __builtin_amdgcn_rcpf(1.f + e);
+  s = x >= 0.f ? inv : e * inv;
+  bce = fmaxf(x, 0.f) - x * y + __logf(1.f + e);
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void dice_bce_partial_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ target,
+                                                               float* __restrict__ part, int B, long HW, int ign, bool vec) {
+  constexpr int NS = 2 + 3 * R;
+  float acc[NS];
+#pragma unroll
+  for (int i = 0; i < NS; i++) acc[i] = 0.f;
+  const long nq = (HW + 3) >> 2, items = (long)B * nq;
+  const int T = R + ign;
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
+    const long b = it / nq, r0 = (it - b * nq) * 4;
+    const int n = vec ? 4 : (int)min(4L, HW - r0);
+    const float* lp = logits + b * R * HW + r0;
+    const uint8_t* tp = target + b * T * HW + r0;
+    const uint32_t iw = ign ? ld4b(tp + (long)R * HW, vec, n) : 0u;
+    bool m[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { m[j] = j < n && ((iw >> (8 * j)) & 0xffu) == 0u; acc[1] += m[j] ? 1.f : 0.f; }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      float x[4];
+      ld4f(lp + (long)r * HW, vec, n, x);
+      const uint32_t yw = ld4b(tp + (long)r * HW, vec, n);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const float y = ((yw >> (8 * j)) & 0xffu) ? 1.f : 0.f;
+        float s, bce;
+        sigmoid_bce(x[j], y, s, bce);
+        acc[0] += m[j] ? bce : 0.f;
+        acc[2 + 3 * r] += m[j] ? s * y : 0.f;
+        acc[2 + 3 * r + 1] += m[j] ? s : 0.f;
+        acc[2 + 3 * r + 2] += m[j] ? y : 0.f;
+      }
+    }
+  }
+  block_partial_store<NS>(acc, part);
+}
+
+// coef = [(ca_r, cb_r) r = 0..R-1, bce_scale]; bce_scale = 1 / n_valid with an ignore channel (pixels, not pixel x region), else
+// 1 / (n_valid R) = the mean over every element; 0 when nothing is valid
+__global__ void dice_bce_coef_kernel(const float* __restrict__ sums, float* __restrict__ loss, float* __restrict__ coef, int R, int ign,
+                                     float smooth, float grad_mult) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float dc = dice_coefs(sums + 2, coef, R, smooth, grad_mult);
+  const float nv = sums[1];
+  const float bce_scale = nv > 0.f ? 1.f / (ign ? nv : nv * (float)R) : 0.f;
+  coef[2 * R] = bce_scale;
+  loss[0] = sums[0] * bce_scale - dc;
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void dice_bce_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ target,
+                                                           const float* __restrict__ coef, const float* __restrict__ gout,
+                                                           float* __restrict__ dlogits, int B, long HW, int ign, bool vec) {
+  const float bce_scale = coef[2 * R];
+  const float go = gout ? gout[0] : 1.f;
+  const long nq = (HW + 3) >> 2, items = (long)B * nq;
+  const int T = R + ign;
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
+    const long b = it / nq, r0 = (it - b * nq) * 4;
+    const int n = vec ? 4 : (int)min(4L, HW - r0);
+    const float* lp = logits + b * R * HW + r0;
+    float* dp = dlogits + b * R * HW + r0;
+    const uint8_t* tp = target + b * T * HW + r0;
+    const uint32_t iw = ign ? ld4b(tp + (long)R * HW, vec, n) : 0u;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const float ca = coef[2 * r], cb = coef[2 * r + 1];
+      float x[4];
+      ld4f(lp + (long)r * HW, vec, n, x);
+      const uint32_t yw = ld4b(tp + (long)r * HW, vec, n);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const bool m = ((iw >> (8 * j)) & 0xffu) == 0u;
+        const float y = ((yw >> (8 * j)) & 0xffu) ? 1.f : 0.f;
+        float s, bce;
+        sigmoid_bce(x[j], y, s, bce);
+        x[j] = m ? go * ((s - y) * bce_scale + (ca * y + cb) * s * (1.f - s)) : 0.f;
+      }
+      st4f(dp + (long)r * HW, vec, n, x);
+    }
+  }
+}
+
+// out (B, R + ign, HW) uint8: plane r = [0 <= label < 64 and bit label of table[r]], plane R = [label == ignore_label]
+__global__ __launch_bounds__(256) void labels_to_regions_kernel(const int64_t* __restrict__ seg, const int64_t* __restrict__ table,
+                                                                uint8_t* __restrict__ out, int B, int R, long HW, int ign, int64_t ignore, bool vec) {
+  uint64_t tb[MAXR];
+#pragma unroll
+  for (int r = 0; r < MAXR; r++) tb[r] = r < R ? (uint64_t)table[r] : 0ull;
+  const long nq = (HW + 3) >> 2, items = (long)B * nq;
+  const int T = R + ign;
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
+    const long b = it / nq, r0 = (it - b * nq) * 4;
+    const int n = vec ? 4 : (int)min(4L, HW - r0);
+    int64_t l[4];
+    ld4l(seg + b * HW + r0, vec, n, -1, l);
+    uint8_t* op = out + b * T * HW + r0;
+#pragma unroll
+    for (int r = 0; r < MAXR; r++) {
+      if (r < R) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) w |= (l[j] >= 0 && l[j] < 64 && ((tb[r] >> l[j]) & 1ull)) ? (1u << (8 * j)) : 0u;
+        st4b(op + (long)r * HW, vec, n, w);
+      }
+    }
+    if (ign) {
+      uint32_t w = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) w |= l[j] == ignore ? (1u << (8 * j)) : 0u;
+      st4b(op + (long)R * HW, vec, n, w);
+    }
+  }
+}
+
+long quad_items(int B, int64_t HW) { return (long)B * ((HW + 3) / 4); }
+// two quads per lane in the sums pass; the partial count is a function of the shape only (same reduction order on every call)
+int masked_grid(long items) { long g = (items + 511) / 512; if (g < 1) g = 1; if (g > 2048) g = 2048; return (int)g; }
+int elem_grid(long items) { long g = (items + 255) / 256; if (g < 1) g = 1; if (g > 8192) g = 8192; return (int)g; }
+// the 4-pixel vector loads / stores: every row (plane of one image) starts on a 16 B (fp32, int64) / 4 B (uint8) boundary
+bool al(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
+
+}  // namespace
+
+#define LOSS_R_SWITCH(R, CALL) \
+  switch (R) { case 1: { CALL(1); break; } case 2: { CALL(2); break; } case 3: { CALL(3); break; } case 4: { CALL(4); break; } \
+               case 5: { CALL(5); break; } case 6: { CALL(6); break; } case 7: { CALL(7); break; } case 8: { CALL(8); break; } \
+               default: return DU_ERR_UNSUPPORTED; }
+
+extern "C" int64_t du_dice_ce_masked_ws_elems(int B, int K, int64_t HW) {
+  if (B <= 0 || K < 2 || K > 8 || HW <= 0) return 0;
+  return (int64_t)masked_grid(quad_items(B, HW)) * (2 + 3 * (K - 1));
+}
+
+extern "C" int du_dice_ce_masked_sums(const float* logits, const int64_t* target, float* sums, int B, int K, int64_t HW,
+                                      int64_t ignore_label, float* ws, int64_t ws_elems, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !target || !sums || !ws || B <= 0 || HW <= 0) return DU_ERR_BAD_ARG;
+  if (K < 2 || K > 8) return DU_ERR_UNSUPPORTED;
+  const int grid = masked_grid(quad_items(B, HW));
+  const int NS = 2 + 3 * (K - 1);
+  if (ws_elems < (int64_t)grid * NS) return DU_ERR_BAD_ARG;
+  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16);
+#define CALL(KK) hipLaunchKernelGGL(dice_ce_masked_partial_kernel<KK>, dim3(grid), dim3(256), 0, st, logits, target, ws, B, (long)HW, ignore_label, vec); \
+                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * (KK - 1)>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
+  LOSS_K_SWITCH(K, CALL)
+#undef CALL
+  return du_check_launch();
+}
+
+extern "C" int du_dice_ce_masked_finish(const float* sums, float* loss, float* coef, int K, float smooth, float grad_mult, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!sums || !loss || !coef) return DU_ERR_BAD_ARG;
+  if (K < 2 || K > 8) return DU_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(dice_ce_masked_coef_kernel, dim3(1), dim3(64), 0, st, sums, loss, coef, K, smooth, grad_mult);
+  return du_check_launch();
+}
+
+extern "C" int du_dice_ce_masked_bwd(const float* logits, const int64_t* target, const float* coef, const float* grad_out, float* dlogits,
+                                     int B, int K, int64_t HW, int64_t ignore_label, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !target || !coef || !dlogits || B <= 0 || HW <= 0) return DU_ERR_BAD_ARG;
+  if (K < 2 || K > 8) return DU_ERR_UNSUPPORTED;
+  const int g = elem_grid(quad_items(B, HW));
+  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16) && al(dlogits, 16);
+#define CALL(KK) hipLaunchKernelGGL(dice_ce_masked_bwd_kernel<KK>, dim3(g), dim3(256), 0, st, logits, target, coef, grad_out, dlogits, B, (long)HW, ignore_label, vec)
+  LOSS_K_SWITCH(K, CALL)
+#undef CALL
+  return du_check_launch();
+}
+
+extern "C" int64_t du_dice_bce_ws_elems(int B, int R, int64_t HW) {
+  if (B <= 0 || R < 1 || R > MAXR || HW <= 0) return 0;
+  return (int64_t)masked_grid(quad_items(B, HW)) * (2 + 3 * R);
+}
+
+extern "C" int du_dice_bce_sums(const float* logits, const uint8_t* target, float* sums, int B, int R, int64_t HW, int has_ignore, float* ws,
+                                int64_t ws_elems, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !target || !sums || !ws || B <= 0 || HW <= 0 || (has_ignore != 0 && has_ignore != 1)) return DU_ERR_BAD_ARG;
+  if (R < 1 || R > MAXR) return DU_ERR_UNSUPPORTED;
+  const int grid = masked_grid(quad_items(B, HW));
+  const int NS = 2 + 3 * R;
+  if (ws_elems < (int64_t)grid * NS) return DU_ERR_BAD_ARG;
+  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 4);
+#define CALL(RR) hipLaunchKernelGGL(dice_bce_partial_kernel<RR>, dim3(grid), dim3(256), 0, st, logits, target, ws, B, (long)HW, has_ignore, vec); \
+                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * RR>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
+  LOSS_R_SWITCH(R, CALL)
+#undef CALL
+  return du_check_launch();
+}
+
+extern "C" int du_dice_bce_finish(const float* sums, float* loss, float* coef, int R, int has_ignore, float smooth, float grad_mult,
+                                  void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!sums || !loss || !coef || (has_ignore != 0 && has_ignore != 1)) return DU_ERR_BAD_ARG;
+  if (R < 1 || R > MAXR) return DU_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(dice_bce_coef_kernel, dim3(1), dim3(64), 0, st, sums, loss, coef, R, has_ignore, smooth, grad_mult);
+  return du_check_launch();
+}
+
+extern "C" int du_dice_bce_bwd(const float* logits, const uint8_t* target, const float* coef, const float* grad_out, float* dlogits, int B,
+                               int R, int64_t HW, int has_ignore, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !target || !coef || !dlogits || B <= 0 || HW <= 0 || (has_ignore != 0 && has_ignore != 1)) return DU_ERR_BAD_ARG;
+  if (R < 1 || R > MAXR) return DU_ERR_UNSUPPORTED;
+  const int g = elem_grid(quad_items(B, HW));
+  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 4) && al(dlogits, 16);
+#define CALL(RR) hipLaunchKernelGGL(dice_bce_bwd_kernel<RR>, dim3(g), dim3(256), 0, st, logits, target, coef, grad_out, dlogits, B, (long)HW, has_ignore, vec)
+  LOSS_R_SWITCH(R, CALL)
+#undef CALL
+  return du_check_launch();
+}
+
+extern "C" int du_labels_to_regions(const int64_t* seg, const int64_t* table, uint8_t* out, int B, int R, int64_t HW, int has_ignore,
+                                    int64_t ignore_label, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!seg || !table || !out || B <= 0 || HW <= 0 || (has_ignore != 0 && has_ignore != 1)) return DU_ERR_BAD_ARG;
+  if (R < 1 || R > MAXR) return DU_ERR_UNSUPPORTED;
+  const bool vec = HW % 4 == 0 && al(seg, 16) && al(out, 4);
+  hipLaunchKernelGGL(labels_to_regions_kernel, dim3(elem_grid(quad_items(B, HW))), dim3(256), 0, st, seg, table, out, B, R, (long)HW,
+                     has_ignore, ignore_label, vec);
+  return du_check_launch();
+}

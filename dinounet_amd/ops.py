@@ -19,7 +19,8 @@ from ._lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SWIGLU, DU_BF16,
                    PLAIN_ROW, STORE_MSDA_PREP, STORE_PIXEL_SHUFFLE2, STORE_QKV_HEADS, STORE_QKV_ROPE, STORE_SLABS, ConvGeom, GemmArgs)
 
 __all__ = ["mm", "linear", "conv2d", "conv_transpose2x2", "norm_act", "layer_norm", "msda", "dwconv3x3",
-           "maxpool3x3s2", "bilinear_add", "bilinear_resize", "squeeze_excite", "dice_ce_loss"]
+           "maxpool3x3s2", "bilinear_add", "bilinear_resize", "squeeze_excite", "dice_ce_loss", "dice_ce_masked_loss", "dice_bce_loss",
+           "labels_to_regions"]
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -2296,6 +2297,122 @@ def dice_ce_loss(logits, target, smooth=1e-5, group=None):
     """logits (B,K,H,W) fp32, target (B,1,H,W) integer labels -> scalar loss (CE - mean soft dice)."""
     _req(logits, target)
     return _DiceCE.apply(logits, target, smooth, group)
+
+
+def _dice_group(sums, group, what):
+    """all-reduce the Dice slice sums[2:] of a masked / region loss (CE / BCE and n_valid stay local) -> grad_mult"""
+    if group is not None and torch.distributed.is_initialized():
+        _small_all_reduce(sums[2:], group, what)
+        return float(torch.distributed.get_world_size(group))
+    return 1.0
+
+
+class _DiceCEMasked(torch.autograd.Function):
+    """DC_and_CE_loss(ignore_label) of the reference trainer (compound_losses.py:31-56; MemoryEfficientSoftDiceLoss with loss_mask,
+    dice.py:72-119) on fp32 NCHW logits, fused like _DiceCE.  CE is the mean over valid pixels and exactly 0 when none is valid, decided on
+    the device (the reference's host-side `num_fg > 0` test would be a sync inside a captured step)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_label, smooth, group):
+        logits = logits.float().contiguous()
+        B, K, H, W = logits.shape
+        HW = H * W
+        tgt = target.reshape(B, HW)
+        if tgt.dtype != torch.int64:
+            tgt = tgt.long()
+        tgt = tgt.contiguous()
+        L = _lib.lib()
+        n = int(L.du_dice_ce_masked_ws_elems(B, K, HW))
+        if n <= 0:
+            raise RuntimeError(f"dinounet_hip: fused Dice+CE with an ignore label supports 2..8 classes, got {K}")
+        ws = torch.empty(n, dtype=torch.float32, device=logits.device)
+        sums = torch.empty(2 + 3 * (K - 1), dtype=torch.float32, device=logits.device)
+        _lib.check(L.du_dice_ce_masked_sums(_p(logits), _p(tgt), _p(sums), B, K, HW, int(ignore_label), _p(ws), n, _st()),
+                   "du_dice_ce_masked_sums")
+        mult = _dice_group(sums, group, "dice_sums")
+        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+        coef = torch.empty(2 * (K - 1) + 1, dtype=torch.float32, device=logits.device)
+        _lib.check(L.du_dice_ce_masked_finish(_p(sums), _p(loss), _p(coef), K, float(smooth), mult, _st()), "du_dice_ce_masked_finish")
+        ctx.save_for_backward(logits, tgt, coef)
+        ctx.ignore_label = int(ignore_label)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, go):
+        logits, tgt, coef = ctx.saved_tensors
+        B, K, H, W = logits.shape
+        dl = torch.empty_like(logits)
+        gof = go.float().contiguous()
+        _lib.check(_lib.lib().du_dice_ce_masked_bwd(_p(logits), _p(tgt), _p(coef), _p(gof), _p(dl), B, K, H * W, ctx.ignore_label, _st()),
+                   "du_dice_ce_masked_bwd")
+        return dl, None, None, None, None
+
+
+def dice_ce_masked_loss(logits, target, ignore_label, smooth=1e-5, group=None):
+    """logits (B,K,H,W) fp32, target (B,1,H,W) integer labels in [0,K) or ignore_label -> scalar loss (masked CE - mean masked soft dice)."""
+    _req(logits, target)
+    return _DiceCEMasked.apply(logits, target, ignore_label, smooth, group)
+
+
+class _DiceBCE(torch.autograd.Function):
+    """DC_and_BCE_loss of the reference trainer for regions (compound_losses.py:59-99; MemoryEfficientSoftDiceLoss with sigmoid, do_bg=True,
+    batch dice) on fp32 NCHW logits and a uint8 one-hot target (B, R + u, H, W), u = 1 with the ignore channel last."""
+
+    @staticmethod
+    def forward(ctx, logits, target, has_ignore, smooth, group):
+        logits = logits.float().contiguous()
+        B, R, H, W = logits.shape
+        HW = H * W
+        u = 1 if has_ignore else 0
+        if target.dtype != torch.uint8 or tuple(target.shape) != (B, R + u, H, W):
+            raise RuntimeError(f"dinounet_hip: region target must be uint8 {(B, R + u, H, W)}, got {target.dtype} {tuple(target.shape)}")
+        tgt = target.contiguous()
+        L = _lib.lib()
+        n = int(L.du_dice_bce_ws_elems(B, R, HW))
+        if n <= 0:
+            raise RuntimeError(f"dinounet_hip: fused Dice+BCE supports 1..8 regions, got {R}")
+        ws = torch.empty(n, dtype=torch.float32, device=logits.device)
+        sums = torch.empty(2 + 3 * R, dtype=torch.float32, device=logits.device)
+        _lib.check(L.du_dice_bce_sums(_p(logits), _p(tgt), _p(sums), B, R, HW, u, _p(ws), n, _st()), "du_dice_bce_sums")
+        mult = _dice_group(sums, group, "dice_sums")
+        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+        coef = torch.empty(2 * R + 1, dtype=torch.float32, device=logits.device)
+        _lib.check(L.du_dice_bce_finish(_p(sums), _p(loss), _p(coef), R, u, float(smooth), mult, _st()), "du_dice_bce_finish")
+        ctx.save_for_backward(logits, tgt, coef)
+        ctx.u = u
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, go):
+        logits, tgt, coef = ctx.saved_tensors
+        B, R, H, W = logits.shape
+        dl = torch.empty_like(logits)
+        gof = go.float().contiguous()
+        _lib.check(_lib.lib().du_dice_bce_bwd(_p(logits), _p(tgt), _p(coef), _p(gof), _p(dl), B, R, H * W, ctx.u, _st()), "du_dice_bce_bwd")
+        return dl, None, None, None, None
+
+
+def dice_bce_loss(logits, target, has_ignore, smooth=1e-5, group=None):
+    """logits (B,R,H,W) fp32, target (B,R+has_ignore,H,W) uint8 {0,1} -> scalar loss (BCE - mean soft dice over the regions)."""
+    _req(logits, target)
+    return _DiceBCE.apply(logits, target, bool(has_ignore), smooth, group)
+
+
+def labels_to_regions(seg, table, ignore_label=None):
+    """seg (B,1,H,W) integer labels, table (R) int64 device bit masks (bit l = label l in region r) -> uint8 (B, R + u, H, W),
+    u = 1 with an ignore label (last plane = [seg == ignore_label])."""
+    _req(seg, table)
+    B, H, W = seg.shape[0], seg.shape[-2], seg.shape[-1]
+    s = seg.reshape(B, H * W)
+    if s.dtype != torch.int64:
+        s = s.long()
+    s = s.contiguous()
+    R = table.numel()
+    u = 0 if ignore_label is None else 1
+    out = torch.empty((B, R + u, H, W), dtype=torch.uint8, device=seg.device)
+    _lib.check(_lib.lib().du_labels_to_regions(_p(s), _p(table.contiguous()), _p(out), B, R, H * W, u,
+                                               0 if ignore_label is None else int(ignore_label), _st()), "du_labels_to_regions")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------

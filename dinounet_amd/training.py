@@ -1,7 +1,8 @@
 """Synthetic-data training-step harness replicating the reference trainer's `train_step`
 (dinounet/training/nnUNetTrainer/nnUNetTrainer.py:899-929): forward -> DC+CE loss -> backward -> clip_grad_norm_(12)
 -> SGD(nesterov, momentum 0.99, wd 3e-5).  On the GPU the loss is the fused Dice+CE kernel pair (csrc/loss.hip) and clip + SGD the
-fused three-launch optimiser (csrc/optim.hip); the torch formula below serves the CPU / many-class path of the gloo tests."""
+fused three-launch optimiser (csrc/optim.hip); the torch formula below serves the CPU / many-class path of the gloo tests.
+build_loss covers the trainer's other label configurations (ignore label, regions: nnUNetTrainer.py:355-365)."""
 import os
 import threading
 
@@ -36,11 +37,14 @@ class _AllReduceSumGrad(torch.autograd.Function):
         return g, None
 
 
-def dc_and_ce_loss(logits, target, smooth=1e-5, ddp=None, group=None):
+def dc_and_ce_loss(logits, target, smooth=1e-5, ddp=None, group=None, ignore_label=None):
     """DC_and_CE_loss (compound_losses.py:8-56) with MemoryEfficientSoftDiceLoss(batch_dice=True, do_bg=False,
     smooth=1e-5) (dice.py:58-119, trainer config nnUNetTrainer.py:363-365).  target (B,1,H,W) integer labels.
     On the GPU (2..8 classes) this is the fused HIP loss (ops.dice_ce_loss); the torch formula below is the CPU / many-class path
-    used by the gloo tests."""
+    used by the gloo tests.  With `ignore_label` the pixels carrying it are masked out (compound_losses.py:38-53): see
+    _dc_and_ce_masked."""
+    if ignore_label is not None:
+        return _dc_and_ce_masked(logits, target, ignore_label, smooth, ddp, group)
     K = logits.shape[1]
     if logits.is_cuda and 2 <= K <= 8:
         from . import ops
@@ -65,6 +69,160 @@ def dc_and_ce_loss(logits, target, smooth=1e-5, ddp=None, group=None):
         sum_gt = _AllReduceSumGrad.apply(sum_gt, group)
     dc = (2 * inter + smooth) / torch.clip(sum_gt + sum_pred + smooth, 1e-8)
     return ce - dc.mean()
+
+
+def _global_dice(inter, sum_pred, sum_gt, smooth, ddp, group):
+    """batch Dice from per-(sample, class) sums (B, C); under DDP the sums are global (dice.py:106-114), the rest stays local"""
+    if ddp is None:
+        ddp = _ddp_default(group)
+    inter, sum_pred, sum_gt = inter.sum(0), sum_pred.sum(0), sum_gt.sum(0)
+    if ddp:
+        inter = _AllReduceSumGrad.apply(inter, group)
+        sum_pred = _AllReduceSumGrad.apply(sum_pred, group)
+        sum_gt = _AllReduceSumGrad.apply(sum_gt, group)
+    return ((2 * inter + smooth) / torch.clip(sum_gt + sum_pred + smooth, 1e-8)).mean()
+
+
+def _dc_and_ce_masked(logits, target, ignore_label, smooth=1e-5, ddp=None, group=None):
+    """DC_and_CE_loss(ignore_label) (compound_losses.py:31-56, dice.py:72-119 with loss_mask, do_bg=False): m = [t != ignore];
+    CE = mean of -log p_t over valid pixels, exactly 0 when there is none -- decided without a host read (the reference's `num_fg > 0`
+    test, :53, is a sync no captured step can hold); Dice over classes 1..K-1 with p and the one-hot target multiplied by m.
+    On the GPU (2..8 classes) the fused HIP loss (ops.dice_ce_masked_loss); the torch formula below is the CPU / many-class path."""
+    K = logits.shape[1]
+    if logits.is_cuda and 2 <= K <= 8:
+        from . import ops
+        if ddp is None:
+            ddp = _ddp_default(group)
+        return ops.dice_ce_masked_loss(logits, target, ignore_label, smooth,
+                                       (group if group is not None else dist.group.WORLD) if ddp else None)
+    lab = target[:, 0].long()
+    m = lab != ignore_label
+    lab0 = torch.where(m, lab, torch.zeros_like(lab))
+    mf = m[:, None].to(logits.dtype)
+    logp = torch.log_softmax(logits, 1)
+    nll = -logp.gather(1, lab0[:, None])
+    ce = (nll * mf).sum() / m.sum().clamp_min(1).to(logits.dtype)       # n_valid = 0: the sum is 0, so is CE
+    prob = torch.softmax(logits, 1)
+    with torch.no_grad():
+        onehot = torch.zeros(prob.shape, device=prob.device, dtype=prob.dtype).scatter_(1, lab0[:, None], 1)[:, 1:] * mf
+        sum_gt = onehot.sum((2, 3))
+    p = prob[:, 1:] * mf
+    return ce - _global_dice((p * onehot).sum((2, 3)), p.sum((2, 3)), sum_gt, smooth, ddp, group)
+
+
+def dc_and_bce_loss(logits, target, use_ignore_label=False, smooth=1e-5, ddp=None, group=None):
+    """DC_and_BCE_loss (compound_losses.py:59-99) with MemoryEfficientSoftDiceLoss(sigmoid, batch_dice=True, do_bg=True, smooth=1e-5)
+    (nnUNetTrainer.py:356-361): region-based training.  logits (B,R,H,W); target the reference's one-hot form (B, R + u, H, W) in {0,1},
+    u = 1 with `use_ignore_label` (ignore channel last, m = 1 - target[:, -1]).  BCE is the mean over every element without an ignore
+    channel, else sum(bce m) / clip(sum m, 1e-8) with the (B,1,H,W) mask broadcast over R -- the denominator counts pixels (:95).
+    On the GPU (1..8 regions) the fused HIP loss (ops.dice_bce_loss; a non-uint8 target is converted once); the torch formula below is
+    the CPU path.  Soft (non-binary) targets are outside this contract."""
+    R = logits.shape[1]
+    u = 1 if use_ignore_label else 0
+    if target.shape[1] != R + u:
+        raise ValueError(f"dc_and_bce_loss: target has {target.shape[1]} channels, expected {R + u} ({R} regions"
+                         f"{' + the ignore channel' if u else ''})")
+    if ddp is None:
+        ddp = _ddp_default(group)
+    if logits.is_cuda and 1 <= R <= 8:
+        from . import ops
+        tgt = target if target.dtype == torch.uint8 else target.to(torch.uint8)
+        return ops.dice_bce_loss(logits, tgt, u, smooth, (group if group is not None else dist.group.WORLD) if ddp else None)
+    y = target[:, :R].to(logits.dtype)
+    bce = F.binary_cross_entropy_with_logits(logits, y, reduction="none")
+    x = torch.sigmoid(logits)
+    if u:
+        mf = (1 - target[:, -1:]).bool().to(logits.dtype)
+        ce = (bce * mf).sum() / torch.clip(mf.sum(), min=1e-8)
+        y = y * mf
+        x = x * mf
+    else:
+        ce = bce.mean()
+    return ce - _global_dice((x * y).sum((2, 3)), x.sum((2, 3)), y.sum((2, 3)), smooth, ddp, group)
+
+
+def _region_masks(regions):
+    """regions (each an int or a tuple of ints, labels 0..63) -> one int64 bit mask per region (bit l = label l belongs to it)"""
+    out = []
+    for r in regions:
+        labs = (r,) if isinstance(r, int) else tuple(r)
+        v = 0
+        for l in labs:
+            if isinstance(l, bool) or not isinstance(l, int) or not 0 <= int(l) <= 63:
+                raise ValueError(f"region label {l!r} outside 0..63")
+            v |= 1 << int(l)
+        out.append(v - (1 << 64) if v >= 1 << 63 else v)        # label 63 is the sign bit of the int64
+    return out
+
+
+def _region_table(regions, device):
+    return torch.tensor(_region_masks(regions), dtype=torch.int64, device=device)
+
+
+def labels_to_regions(seg, regions, ignore_label=None, table=None):
+    """ConvertSegmentationToRegionsTransform (region_based_training.py:7-37; the ignore label appended as the last region,
+    nnUNetTrainer.py:764-767): seg (B,1,H,W) integer labels -> uint8 (B, R + u, H, W), plane r = [seg in regions[r]], u = 1 with an
+    ignore label, last plane = [seg == ignore_label].  A label outside 0..63 is in no region.  On the GPU the HIP kernel
+    (du_labels_to_regions) with the regions as a device table of bit masks (`table`: a prepared one, e.g. build_loss's); on the CPU
+    torch.isin."""
+    if seg.is_cuda:
+        from . import ops
+        if table is None:
+            table = _region_table(regions, seg.device)
+        return ops.labels_to_regions(seg, table, ignore_label)
+    s = seg[:, 0]
+    planes = []
+    for r in regions:
+        labs = torch.tensor([r] if isinstance(r, int) else list(r), dtype=s.dtype)
+        planes.append(torch.isin(s, labs))
+    if ignore_label is not None:
+        planes.append(s == ignore_label)
+    return torch.stack(planes, 1).to(torch.uint8)
+
+
+class SegLoss(torch.nn.Module):
+    """What nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365) returns for 2D, no deep supervision, batch Dice: DC_and_CE_loss (plain
+    labels or with an ignore label) or DC_and_BCE_loss (regions, with or without an ignore label).  Called as loss(logits, target) with
+    integer label maps (B,1,H,W) in both modes; in region mode the labels become the one-hot region target on the device inside the same
+    step (labels_to_regions with the table built here, at construction, outside any capture)."""
+
+    def __init__(self, num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None):
+        super().__init__()
+        if ignore_label is not None:
+            if isinstance(ignore_label, bool) or not isinstance(ignore_label, int):
+                raise ValueError(f"ignore_label must be an int, got {ignore_label!r}")
+            if ignore_label < num_classes:
+                raise ValueError(f"ignore_label {ignore_label} must not be a class index (< num_classes = {num_classes})")
+        self.num_classes, self.ignore_label, self.smooth, self.ddp, self.group = num_classes, ignore_label, smooth, ddp, group
+        self.regions = None if regions is None else [r if isinstance(r, int) else tuple(r) for r in regions]
+        if self.regions is not None:
+            if not 1 <= len(self.regions) <= 8:
+                raise ValueError(f"region-based loss: 1..8 regions supported, got {len(self.regions)}")
+            if len(self.regions) != num_classes:
+                raise ValueError(f"region-based loss: num_classes (network outputs) {num_classes} != {len(self.regions)} regions")
+            masks = _region_masks(self.regions)                  # ValueError for a label outside 0..63
+            if ignore_label is not None and 0 <= ignore_label <= 63 and any((m >> ignore_label) & 1 for m in masks):
+                raise ValueError(f"ignore_label {ignore_label} lies inside a region")
+            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+            self.register_buffer("table", _region_table(self.regions, dev), persistent=False)
+        self.mode = "regions" if self.regions is not None else ("softmax_ignore" if ignore_label is not None else "softmax")
+
+    def forward(self, logits, target):
+        if self.regions is None:
+            return dc_and_ce_loss(logits, target, self.smooth, ddp=self.ddp, group=self.group, ignore_label=self.ignore_label)
+        table = self.table if self.table.device == target.device else None
+        if target.is_cuda and table is None:
+            raise RuntimeError(f"SegLoss: region table lives on {self.table.device}, target on {target.device} (move the module with .to())")
+        onehot = labels_to_regions(target, self.regions, self.ignore_label, table=table)
+        return dc_and_bce_loss(logits, onehot, self.ignore_label is not None, self.smooth, ddp=self.ddp, group=self.group)
+
+
+def build_loss(num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None):
+    """nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365) for this package: the loss module for plain labels, labels with an ignore
+    label, or regions (each an int or a tuple of ints; num_classes = number of network outputs = len(regions)).  Validated on the host:
+    ValueError for an ignore label below num_classes, more than 8 regions, a region label outside 0..63 or an ignore label inside a
+    region.  Pass the result to TrainStep(loss=...)."""
+    return SegLoss(num_classes, regions=regions, ignore_label=ignore_label, smooth=smooth, ddp=ddp, group=group)
 
 
 class _CaptureSegments:
@@ -134,9 +292,10 @@ class TrainStep:
     live under replay because torch registers the generator's Philox offset with the graph."""
 
     def __init__(self, net, optimizer, params, x_shape, tgt_shape, device, reducer=None, max_norm=12.0, graph=True, warmup=3,
-                 ddp_loss=None, comm_outside_graph=None):
+                 ddp_loss=None, comm_outside_graph=None, loss=None):
         self.net, self.opt, self.params, self.reducer, self.max_norm = net, optimizer, params, reducer, max_norm
         self.ddp_loss = ddp_loss         # None: batch-Dice sums all-reduced iff world size > 1 (dice.py:58-119 with ddp=True)
+        self.loss_fn = loss              # None: dc_and_ce_loss on plain labels; else a build_loss module, called as loss(logits, tgt)
         if comm_outside_graph is None:
             comm_outside_graph = os.environ.get("DINOUNET_COMM_OUTSIDE_GRAPH", "0") == "1"
         self.comm_outside_graph = bool(comm_outside_graph) and reducer is not None
@@ -155,7 +314,10 @@ class TrainStep:
     def _step(self):
         self.opt.zero_grad(set_to_none=True)
         logits = self.net(self.x)
-        loss = dc_and_ce_loss(logits, self.tgt, ddp=self.ddp_loss)
+        if self.loss_fn is None:
+            loss = dc_and_ce_loss(logits, self.tgt, ddp=self.ddp_loss)
+        else:
+            loss = self.loss_fn(logits, self.tgt)
         loss.backward()
         if logits.is_cuda:
             from . import ops

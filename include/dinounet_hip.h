@@ -31,6 +31,10 @@
  *   du_msda_prep / du_msda_prep_bwd <- ms_deform_attn.py:188-197
  *   du_dice_ce_*                  <- DC_and_CE_loss (training/loss/compound_losses.py:8-56, dice.py:58-119), the loss nnUNetTrainer.train_step
  *          applies to the logits (nnUNetTrainer.py:917); "next" row of the scope table
+ *   du_dice_ce_masked_*, du_dice_bce_*, du_labels_to_regions
+ *       <- the ignore-label and region configurations of nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365):
+ *          DC_and_CE_loss(ignore_label) (compound_losses.py:31-56), DC_and_BCE_loss (compound_losses.py:83-99),
+ *          ConvertSegmentationToRegionsTransform (nnUNetTrainer.py:766-767)
  */
 #ifndef DINOUNET_HIP_H
 #define DINOUNET_HIP_H
@@ -401,6 +405,40 @@ int du_dice_ce_finish(const float* sums, float* loss, float* coef, int K, int64_
 /* dlogits (B,K,H,W) fp32 = grad_out[0] * d loss / d logits (grad_out: device scalar or NULL for 1) */
 int du_dice_ce_bwd(const float* logits, const int64_t* target, const float* coef, const float* grad_out, float* dlogits, int B, int K,
                    int64_t HW, void* stream);
+
+/* ---- trainer loss with an ignore label: DC_and_CE_loss(ignore_label) (training/loss/compound_losses.py:31-56, dice.py:72-119 with
+        loss_mask; nnUNetTrainer._build_loss, nnUNetTrainer.py:363-365) ---- */
+/* logits (B,K,H,W) fp32, target (B,H*W) int64 in [0,K) or ignore_label, K in [2,8] (DU_ERR_UNSUPPORTED otherwise).  m = [t != ignore].
+   sums: 2 + 3(K-1) floats = [sum m (-log p_t), n_valid, (I_c, P_c, G_c) c = 1..K-1], every term multiplied by m.  scratch:
+   du_dice_ce_masked_ws_elems floats.  Under data parallelism the caller all-reduces sums[2:] only (CE and n_valid stay local). */
+int64_t du_dice_ce_masked_ws_elems(int B, int K, int64_t HW);
+int du_dice_ce_masked_sums(const float* logits, const int64_t* target, float* sums, int B, int K, int64_t HW, int64_t ignore_label,
+                           float* ws, int64_t ws_elems, void* stream);
+/* loss (1 float) = CE_sum * ce_scale - mean_c dice_c with ce_scale = 1/n_valid, or 0 when n_valid = 0 (compound_losses.py:52-53, decided
+   on the device); coef (2(K-1) + 1) = dice backward coefficients then ce_scale; grad_mult = world size when sums[2:] were all-reduced */
+int du_dice_ce_masked_finish(const float* sums, float* loss, float* coef, int K, float smooth, float grad_mult, void* stream);
+/* dlogits = grad_out[0] * d loss / d logits; exactly 0 in every channel of an ignored pixel */
+int du_dice_ce_masked_bwd(const float* logits, const int64_t* target, const float* coef, const float* grad_out, float* dlogits, int B,
+                          int K, int64_t HW, int64_t ignore_label, void* stream);
+
+/* ---- trainer loss for regions: DC_and_BCE_loss (training/loss/compound_losses.py:59-99; MemoryEfficientSoftDiceLoss with sigmoid,
+        do_bg=True, dice.py:58-119; nnUNetTrainer.py:356-361) ---- */
+/* logits (B,R,H,W) fp32, target (B,R+has_ignore,H*W) uint8 in {0,1}, R in [1,8] (DU_ERR_UNSUPPORTED otherwise).  With has_ignore the last
+   target plane is the ignore channel and m = 1 - target[:, R], else m = 1.  sums: 2 + 3R floats = [sum m bce, n_valid (pixels),
+   (I_r, P_r, G_r) r = 0..R-1].  Under data parallelism the caller all-reduces sums[2:] only. */
+int64_t du_dice_bce_ws_elems(int B, int R, int64_t HW);
+int du_dice_bce_sums(const float* logits, const uint8_t* target, float* sums, int B, int R, int64_t HW, int has_ignore, float* ws,
+                     int64_t ws_elems, void* stream);
+/* loss (1 float) = BCE_sum * bce_scale - mean_r dice_r, bce_scale = 1/n_valid with has_ignore (compound_losses.py:95: the mask is
+   (B,1,H,W), the denominator counts pixels), else 1/(n_valid R) (the mean over every element), 0 when n_valid = 0; coef (2R + 1) */
+int du_dice_bce_finish(const float* sums, float* loss, float* coef, int R, int has_ignore, float smooth, float grad_mult, void* stream);
+int du_dice_bce_bwd(const float* logits, const uint8_t* target, const float* coef, const float* grad_out, float* dlogits, int B, int R,
+                    int64_t HW, int has_ignore, void* stream);
+/* ConvertSegmentationToRegionsTransform (data_augmentation/custom_transforms/region_based_training.py:7-37, nnUNetTrainer.py:764-767):
+   seg (B,H*W) int64, table (R) int64 DEVICE bit masks (bit l set = label l belongs to region r; labels 0..63, any other label is in no
+   region), out (B,R+has_ignore,H*W) uint8: plane r = [seg in region r], plane R = [seg == ignore_label] */
+int du_labels_to_regions(const int64_t* seg, const int64_t* table, uint8_t* out, int B, int R, int64_t HW, int has_ignore,
+                         int64_t ignore_label, void* stream);
 
 /* ---- FAPM FiLM modulation (dinounet_training.py:427-429): z = gamma * z_specific + beta; gb (rows,2R) = [gamma|beta], z2 (rows,2R) =
         [z_shared|z_specific], z (rows,R).  Backward writes all of dgb and the z_specific half of dz2. ---- */
