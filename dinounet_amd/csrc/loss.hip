@@ -12,14 +12,75 @@ namespace {
 
 constexpr int MAXK = 16;
 
+// Validation counts (COUNTS instantiations of the partial kernels; nnUNetTrainer.validation_step, nnUNetTrainer.py:971-994 with
+// get_tp_fp_fn_tn, dice.py:122-167): per class / region three int32 lane counters (hits, predicted, labelled) over the valid pixels, added
+// over the wave and the block as integers into one row of 3C int32 per block (cpart).  counts_sum_kernel adds the rows in int64 and turns
+// them into tp = hits, fp = predicted - hits, fn = labelled - hits.  The float code of a COUNTS instantiation is the text of the COUNTS =
+// false one, so the sums (and the loss `finish` makes of them) are the training forward's, bit for bit.
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <int NC>
+__device__ __forceinline__ void block_counts_store(int (&cnt)[NC], int* __restrict__ cpart) {
+  __shared__ int cred[4][NC];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < NC; i++) {
+    const int s = wave_sum_i(cnt[i]);
+    if (lane == 0) cred[wave][i] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NC) cpart[(long)blockIdx.x * NC + threadIdx.x] = cred[0][threadIdx.x] + cred[1][threadIdx.x] + cred[2][threadIdx.x] + cred[3][threadIdx.x];
+}
+// torch.argmax over the class axis: the lowest index among equal maxima (finite logits)
+template <int K, typename F>
+__device__ __forceinline__ int argmax_first(F&& x) {
+  int pred = 0;
+  float best = x(0);
+#pragma unroll
+  for (int k = 1; k < K; k++) { const float xk = x(k); if (xk > best) { best = xk; pred = k; } }
+  return pred;
+}
+
+// second stage of the counts: ONE block adds the per-block rows (blocks x 3C int32) in int64, fixed order; counts (3, C) int64 =
+// this step's (tp, fp, fn), accum (3, C) int64 += the same (NULL: skipped)
+__global__ __launch_bounds__(256) void counts_sum_kernel(const int* __restrict__ cpart, int64_t* __restrict__ counts,
+                                                         int64_t* __restrict__ accum, int blocks, int C) {
+  __shared__ long long red[3 * 8][4];
+  __shared__ long long tot[3 * 8];
+  const int NC = 3 * C;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = 0; i < NC; i++) {
+    long long a = 0;
+    for (int b = threadIdx.x; b < blocks; b += 256) a += (long long)cpart[(long)b * NC + i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    if (lane == 0) red[i][wave] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x < NC) tot[threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+  __syncthreads();
+  if (threadIdx.x < NC) {
+    const int row = threadIdx.x / C, c = threadIdx.x - row * C;
+    const long long v = row == 0 ? tot[c] : tot[row * C + c] - tot[c];
+    counts[threadIdx.x] = (int64_t)v;
+    if (accum) accum[threadIdx.x] += (int64_t)v;
+  }
+}
+
 // sums layout: [0] = sum of -log p_target, then for c = 1..K-1: [1 + 3(c-1) + {0,1,2}] = (I_c, P_c, G_c)
-template <int K>
+template <int K, bool COUNTS>
 __global__ __launch_bounds__(256) void dice_ce_partial_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                              float* __restrict__ part, int B, long HW) {
+                                                              float* __restrict__ part, int* __restrict__ cpart, int B, long HW) {
   constexpr int NS = 1 + 3 * (K - 1);
   float acc[NS];
 #pragma unroll
   for (int i = 0; i < NS; i++) acc[i] = 0.f;
+  int cnt[COUNTS ? 3 * K : 1];
+#pragma unroll
+  for (int i = 0; i < (COUNTS ? 3 * K : 1); i++) cnt[i] = 0;
   const long npix = (long)B * HW;
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
     const long b = p / HW, r = p - b * HW;
@@ -28,11 +89,20 @@ __global__ __launch_bounds__(256) void dice_ce_partial_kernel(const float* __res
     float mx = -INFINITY;
 #pragma unroll
     for (int k = 0; k < K; k++) { v[k] = lp[(long)k * HW]; mx = fmaxf(mx, v[k]); }
+    const int t = (int)target[p];
+    if constexpr (COUNTS) {
+      const int pred = argmax_first<K>([&](int k) { return v[k]; });
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+        cnt[k] += (pred == k && t == k) ? 1 : 0;
+        cnt[K + k] += pred == k ? 1 : 0;
+        cnt[2 * K + k] += t == k ? 1 : 0;
+      }
+    }
     float se = 0.f;
 #pragma unroll
     for (int k = 0; k < K; k++) { v[k] = __expf(v[k] - mx); se += v[k]; }
     const float inv = 1.f / se;
-    const int t = (int)target[p];
 #pragma unroll
     for (int k = 0; k < K; k++) {
       const float pk = v[k] * inv;
@@ -52,6 +122,7 @@ __global__ __launch_bounds__(256) void dice_ce_partial_kernel(const float* __res
   }
   __syncthreads();
   if (threadIdx.x < NS) part[(long)blockIdx.x * NS + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  if constexpr (COUNTS) block_counts_store<3 * K>(cnt, cpart);
 }
 
 __global__ __launch_bounds__(256) void dice_ce_sum_kernel(const float* __restrict__ part, float* __restrict__ sums, int blocks, int NS) {
@@ -144,7 +215,7 @@ extern "C" int du_dice_ce_sums(const float* logits, const int64_t* target, float
   const int grid = loss_grid((long)B * HW);
   const int NS = 1 + 3 * (K - 1);
   if (ws_elems < (int64_t)grid * NS) return DU_ERR_BAD_ARG;
-#define CALL(KK) hipLaunchKernelGGL(dice_ce_partial_kernel<KK>, dim3(grid), dim3(256), 0, st, logits, target, ws, B, (long)HW)
+#define CALL(KK) hipLaunchKernelGGL((dice_ce_partial_kernel<KK, false>), dim3(grid), dim3(256), 0, st, logits, target, ws, (int*)nullptr, B, (long)HW)
   LOSS_K_SWITCH(K, CALL)
 #undef CALL
   hipLaunchKernelGGL(dice_ce_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid, NS);
@@ -266,13 +337,17 @@ __global__ __launch_bounds__(256) void partial_rows_sum_kernel(const float* __re
   block_partial_store<NS>(acc, sums);     // gridDim.x == 1: row 0 of `sums`
 }
 
-template <int K>
+template <int K, bool COUNTS>
 __global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                                     float* __restrict__ part, int B, long HW, int64_t ignore, bool vec) {
+                                                                     float* __restrict__ part, int* __restrict__ cpart, int B, long HW,
+                                                                     int64_t ignore, bool vec) {
   constexpr int NS = 2 + 3 * (K - 1);
   float acc[NS];
 #pragma unroll
   for (int i = 0; i < NS; i++) acc[i] = 0.f;
+  int cnt[COUNTS ? 3 * K : 1];
+#pragma unroll
+  for (int i = 0; i < (COUNTS ? 3 * K : 1); i++) cnt[i] = 0;
   const long nq = (HW + 3) >> 2, items = (long)B * nq;
   for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
     const long b = it / nq, r0 = (it - b * nq) * 4;
@@ -289,6 +364,15 @@ __global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float
       float mx = -INFINITY;
 #pragma unroll
       for (int k = 0; k < K; k++) mx = fmaxf(mx, v[k][j]);
+      if constexpr (COUNTS) {       // an ignored pixel (and the padding of a partial quad) adds to no count
+        const int pred = argmax_first<K>([&](int k) { return v[k][j]; });
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+          cnt[k] += (valid && pred == k && t[j] == k) ? 1 : 0;
+          cnt[K + k] += (valid && pred == k) ? 1 : 0;
+          cnt[2 * K + k] += (valid && t[j] == k) ? 1 : 0;
+        }
+      }
       float e[K], se = 0.f, xt = mx;
 #pragma unroll
       for (int k = 0; k < K; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
@@ -306,6 +390,7 @@ __global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float
     }
   }
   block_partial_store<NS>(acc, part);
+  if constexpr (COUNTS) block_counts_store<3 * K>(cnt, cpart);
 }
 
 // per-class dice coefficients shared by both configurations: loss -= mean_c dc_c; d loss / d q_c(pixel) = m (ca_c y_c + cb_c), q = the
@@ -393,13 +478,19 @@ __device__ __forceinline__ void sigmoid_bce(float x, float y, float& s, float& b
   bce = fmaxf(x, 0.f) - x * y + __logf(1.f + e);
 }
 
-template <int R>
+// COUNTS: region r is predicted where x > 0.  The reference thresholds sigmoid(x) > 0.5 (nnUNetTrainer.py:974); torch's fp32 sigmoid
+// rounds to exactly 0.5 for 0 < x < ~1.2e-7, so the two predicates differ only inside that band (and agree at x = 0: not predicted)
+template <int R, bool COUNTS>
 __global__ __launch_bounds__(256) void dice_bce_partial_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ target,
-                                                               float* __restrict__ part, int B, long HW, int ign, bool vec) {
+                                                               float* __restrict__ part, int* __restrict__ cpart, int B, long HW, int ign,
+                                                               bool vec) {
   constexpr int NS = 2 + 3 * R;
   float acc[NS];
 #pragma unroll
   for (int i = 0; i < NS; i++) acc[i] = 0.f;
+  int cnt[COUNTS ? 3 * R : 1];
+#pragma unroll
+  for (int i = 0; i < (COUNTS ? 3 * R : 1); i++) cnt[i] = 0;
   const long nq = (HW + 3) >> 2, items = (long)B * nq;
   const int T = R + ign;
   for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
@@ -419,6 +510,12 @@ __global__ __launch_bounds__(256) void dice_bce_partial_kernel(const float* __re
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const float y = ((yw >> (8 * j)) & 0xffu) ? 1.f : 0.f;
+        if constexpr (COUNTS) {
+          const bool pred = x[j] > 0.f, lab = ((yw >> (8 * j)) & 0xffu) != 0u;
+          cnt[r] += (m[j] && pred && lab) ? 1 : 0;
+          cnt[R + r] += (m[j] && pred) ? 1 : 0;
+          cnt[2 * R + r] += (m[j] && lab) ? 1 : 0;
+        }
         float s, bce;
         sigmoid_bce(x[j], y, s, bce);
         acc[0] += m[j] ? bce : 0.f;
@@ -429,6 +526,7 @@ __global__ __launch_bounds__(256) void dice_bce_partial_kernel(const float* __re
     }
   }
   block_partial_store<NS>(acc, part);
+  if constexpr (COUNTS) block_counts_store<3 * R>(cnt, cpart);
 }
 
 // coef = [(ca_r, cb_r) r = 0..R-1, bce_scale]; bce_scale = 1 / n_valid with an ignore channel (pixels, not pixel x region), else
@@ -537,7 +635,7 @@ extern "C" int du_dice_ce_masked_sums(const float* logits, const int64_t* target
   const int NS = 2 + 3 * (K - 1);
   if (ws_elems < (int64_t)grid * NS) return DU_ERR_BAD_ARG;
   const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16);
-#define CALL(KK) hipLaunchKernelGGL(dice_ce_masked_partial_kernel<KK>, dim3(grid), dim3(256), 0, st, logits, target, ws, B, (long)HW, ignore_label, vec); \
+#define CALL(KK) hipLaunchKernelGGL((dice_ce_masked_partial_kernel<KK, false>), dim3(grid), dim3(256), 0, st, logits, target, ws, (int*)nullptr, B, (long)HW, ignore_label, vec); \
                  hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * (KK - 1)>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
   LOSS_K_SWITCH(K, CALL)
 #undef CALL
@@ -579,7 +677,7 @@ extern "C" int du_dice_bce_sums(const float* logits, const uint8_t* target, floa
   const int NS = 2 + 3 * R;
   if (ws_elems < (int64_t)grid * NS) return DU_ERR_BAD_ARG;
   const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 4);
-#define CALL(RR) hipLaunchKernelGGL(dice_bce_partial_kernel<RR>, dim3(grid), dim3(256), 0, st, logits, target, ws, B, (long)HW, has_ignore, vec); \
+#define CALL(RR) hipLaunchKernelGGL((dice_bce_partial_kernel<RR, false>), dim3(grid), dim3(256), 0, st, logits, target, ws, (int*)nullptr, B, (long)HW, has_ignore, vec); \
                  hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * RR>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
   LOSS_R_SWITCH(R, CALL)
 #undef CALL
@@ -616,5 +714,83 @@ extern "C" int du_labels_to_regions(const int64_t* seg, const int64_t* table, ui
   const bool vec = HW % 4 == 0 && al(seg, 16) && al(out, 4);
   hipLaunchKernelGGL(labels_to_regions_kernel, dim3(elem_grid(quad_items(B, HW))), dim3(256), 0, st, seg, table, out, B, R, (long)HW,
                      has_ignore, ignore_label, vec);
+  return du_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Validation pass (nnUNetTrainer.validation_step, nnUNetTrainer.py:946-1008): the sums of the matching training loss (same layout, same
+// bits: the COUNTS instantiations share the float code; the caller runs the matching *_finish on them) and the exact tp / fp / fn of the
+// hard prediction, from ONE read of the logits.  counts (3, C) int64 = this step's [tp | fp | fn] over all C = K classes / R regions
+// (the host drops the background, :999-1006); accum (3, C) int64 += counts (NULL: none).  ws: the float partial rows, then the int32 count
+// rows (4-byte elements both).  int32 block partials: B * HW < 2^31.
+namespace {
+bool counts_fit(int B, int64_t HW) { return (int64_t)B * HW < ((int64_t)1 << 31); }
+}  // namespace
+
+extern "C" int64_t du_val_dice_ce_ws_elems(int B, int K, int64_t HW) {
+  if (B <= 0 || K < 2 || K > 8 || HW <= 0) return 0;
+  return (int64_t)loss_grid((long)B * HW) * (1 + 3 * (K - 1) + 3 * K);
+}
+
+extern "C" int du_val_dice_ce(const float* logits, const int64_t* target, float* sums, int64_t* counts, int64_t* accum, int B, int K,
+                              int64_t HW, float* ws, int64_t ws_elems, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !target || !sums || !counts || !ws || B <= 0 || HW <= 0) return DU_ERR_BAD_ARG;
+  if (K < 2 || K > 8 || !counts_fit(B, HW)) return DU_ERR_UNSUPPORTED;
+  const int grid = loss_grid((long)B * HW);
+  const int NS = 1 + 3 * (K - 1);
+  if (ws_elems < (int64_t)grid * (NS + 3 * K)) return DU_ERR_BAD_ARG;
+  int* cws = reinterpret_cast<int*>(ws + (long)grid * NS);
+#define CALL(KK) hipLaunchKernelGGL((dice_ce_partial_kernel<KK, true>), dim3(grid), dim3(256), 0, st, logits, target, ws, cws, B, (long)HW)
+  LOSS_K_SWITCH(K, CALL)
+#undef CALL
+  hipLaunchKernelGGL(dice_ce_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid, NS);
+  hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, K);
+  return du_check_launch();
+}
+
+extern "C" int64_t du_val_dice_ce_masked_ws_elems(int B, int K, int64_t HW) {
+  if (B <= 0 || K < 2 || K > 8 || HW <= 0) return 0;
+  return (int64_t)masked_grid(quad_items(B, HW)) * (2 + 3 * (K - 1) + 3 * K);
+}
+
+extern "C" int du_val_dice_ce_masked(const float* logits, const int64_t* target, float* sums, int64_t* counts, int64_t* accum, int B,
+                                     int K, int64_t HW, int64_t ignore_label, float* ws, int64_t ws_elems, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !target || !sums || !counts || !ws || B <= 0 || HW <= 0) return DU_ERR_BAD_ARG;
+  if (K < 2 || K > 8 || !counts_fit(B, HW)) return DU_ERR_UNSUPPORTED;
+  const int grid = masked_grid(quad_items(B, HW));
+  const int NS = 2 + 3 * (K - 1);
+  if (ws_elems < (int64_t)grid * (NS + 3 * K)) return DU_ERR_BAD_ARG;
+  int* cws = reinterpret_cast<int*>(ws + (long)grid * NS);
+  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16);
+#define CALL(KK) hipLaunchKernelGGL((dice_ce_masked_partial_kernel<KK, true>), dim3(grid), dim3(256), 0, st, logits, target, ws, cws, B, (long)HW, ignore_label, vec); \
+                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * (KK - 1)>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
+  LOSS_K_SWITCH(K, CALL)
+#undef CALL
+  hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, K);
+  return du_check_launch();
+}
+
+extern "C" int64_t du_val_dice_bce_ws_elems(int B, int R, int64_t HW) {
+  if (B <= 0 || R < 1 || R > MAXR || HW <= 0) return 0;
+  return (int64_t)masked_grid(quad_items(B, HW)) * (2 + 3 * R + 3 * R);
+}
+
+extern "C" int du_val_dice_bce(const float* logits, const uint8_t* target, float* sums, int64_t* counts, int64_t* accum, int B, int R,
+                               int64_t HW, int has_ignore, float* ws, int64_t ws_elems, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !target || !sums || !counts || !ws || B <= 0 || HW <= 0 || (has_ignore != 0 && has_ignore != 1)) return DU_ERR_BAD_ARG;
+  if (R < 1 || R > MAXR || !counts_fit(B, HW)) return DU_ERR_UNSUPPORTED;
+  const int grid = masked_grid(quad_items(B, HW));
+  const int NS = 2 + 3 * R;
+  if (ws_elems < (int64_t)grid * (NS + 3 * R)) return DU_ERR_BAD_ARG;
+  int* cws = reinterpret_cast<int*>(ws + (long)grid * NS);
+  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 4);
+#define CALL(RR) hipLaunchKernelGGL((dice_bce_partial_kernel<RR, true>), dim3(grid), dim3(256), 0, st, logits, target, ws, cws, B, (long)HW, has_ignore, vec); \
+                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * RR>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
+  LOSS_R_SWITCH(R, CALL)
+#undef CALL
+  hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, R);
   return du_check_launch();
 }

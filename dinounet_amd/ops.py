@@ -20,7 +20,7 @@ from ._lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SWIGLU, DU_BF16,
 
 __all__ = ["mm", "linear", "conv2d", "conv_transpose2x2", "norm_act", "layer_norm", "msda", "dwconv3x3",
            "maxpool3x3s2", "bilinear_add", "bilinear_resize", "squeeze_excite", "dice_ce_loss", "dice_ce_masked_loss", "dice_bce_loss",
-           "labels_to_regions"]
+           "labels_to_regions", "val_dice_ce", "val_dice_bce"]
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -2413,6 +2413,84 @@ def labels_to_regions(seg, table, ignore_label=None):
     _lib.check(_lib.lib().du_labels_to_regions(_p(s), _p(table.contiguous()), _p(out), B, R, H * W, u,
                                                0 if ignore_label is None else int(ignore_label), _st()), "du_labels_to_regions")
     return out
+
+
+def _val_bufs(C_, counts, accum, device):
+    if counts is None:
+        counts = torch.empty((3, C_), dtype=torch.int64, device=device)
+    for t, what in ((counts, "counts"), (accum, "accum")):
+        if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (3, C_) or not t.is_contiguous() or t.device != device):
+            raise RuntimeError(f"dinounet_hip: validation {what} must be a contiguous int64 {(3, C_)} tensor on {device}")
+    return counts
+
+
+@torch.no_grad()
+def val_dice_ce(logits, target, ignore_label=None, smooth=1e-5, group=None, counts=None, accum=None):
+    """Validation pass of the softmax configurations (nnUNetTrainer.validation_step, nnUNetTrainer.py:946-1008): logits (B,K,H,W) fp32,
+    target (B,1,H,W) integer labels -> (loss, counts).  loss: the forward value of dice_ce_loss / dice_ce_masked_loss on the same tensors,
+    bit for bit (same per-pixel code, same reduction, same finish kernel).  counts (3, K) int64 = [tp | fp | fn] of the argmax prediction
+    over the pixels that do not carry `ignore_label`; `accum` (3, K) int64, if given, is incremented by them on the device."""
+    _req(logits, target, counts, accum)
+    logits = logits.float().contiguous()
+    B, K, H, W = logits.shape
+    HW = H * W
+    tgt = target.reshape(B, HW)
+    if tgt.dtype != torch.int64:
+        tgt = tgt.long()
+    tgt = tgt.contiguous()
+    L = _lib.lib()
+    masked = ignore_label is not None
+    n = int((L.du_val_dice_ce_masked_ws_elems if masked else L.du_val_dice_ce_ws_elems)(B, K, HW))
+    if n <= 0:
+        raise RuntimeError(f"dinounet_hip: the fused validation pass supports 2..8 classes, got {K}")
+    counts = _val_bufs(K, counts, accum, logits.device)
+    ws = torch.empty(n, dtype=torch.float32, device=logits.device)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    if masked:
+        sums = torch.empty(2 + 3 * (K - 1), dtype=torch.float32, device=logits.device)
+        coef = torch.empty(2 * (K - 1) + 1, dtype=torch.float32, device=logits.device)
+        _lib.check(L.du_val_dice_ce_masked(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, K, HW, int(ignore_label), _p(ws), n,
+                                           _st()), "du_val_dice_ce_masked")
+        mult = _dice_group(sums, group, "dice_sums")
+        _lib.check(L.du_dice_ce_masked_finish(_p(sums), _p(loss), _p(coef), K, float(smooth), mult, _st()), "du_dice_ce_masked_finish")
+    else:
+        sums = torch.empty(1 + 3 * (K - 1), dtype=torch.float32, device=logits.device)
+        coef = torch.empty(2 * (K - 1), dtype=torch.float32, device=logits.device)
+        _lib.check(L.du_val_dice_ce(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, K, HW, _p(ws), n, _st()), "du_val_dice_ce")
+        mult = 1.0
+        if group is not None and torch.distributed.is_initialized():
+            _small_all_reduce(sums[1:], group, "dice_sums")
+            mult = float(torch.distributed.get_world_size(group))
+        _lib.check(L.du_dice_ce_finish(_p(sums), _p(loss), _p(coef), K, B * HW, float(smooth), mult, _st()), "du_dice_ce_finish")
+    return loss.view(()), counts
+
+
+@torch.no_grad()
+def val_dice_bce(logits, target, has_ignore, smooth=1e-5, group=None, counts=None, accum=None):
+    """Validation pass of the region configuration: logits (B,R,H,W) fp32, target (B,R+has_ignore,H,W) uint8 one-hot planes ->
+    (loss, counts).  loss: the forward value of dice_bce_loss, bit for bit; counts (3, R) int64 = [tp | fp | fn] of the prediction x > 0
+    (the reference's sigmoid(x) > 0.5, nnUNetTrainer.py:974, outside 0 < x < ~1.2e-7) over the pixels whose ignore plane is clear."""
+    _req(logits, target, counts, accum)
+    logits = logits.float().contiguous()
+    B, R, H, W = logits.shape
+    HW = H * W
+    u = 1 if has_ignore else 0
+    if target.dtype != torch.uint8 or tuple(target.shape) != (B, R + u, H, W):
+        raise RuntimeError(f"dinounet_hip: region target must be uint8 {(B, R + u, H, W)}, got {target.dtype} {tuple(target.shape)}")
+    tgt = target.contiguous()
+    L = _lib.lib()
+    n = int(L.du_val_dice_bce_ws_elems(B, R, HW))
+    if n <= 0:
+        raise RuntimeError(f"dinounet_hip: the fused validation pass supports 1..8 regions, got {R}")
+    counts = _val_bufs(R, counts, accum, logits.device)
+    ws = torch.empty(n, dtype=torch.float32, device=logits.device)
+    sums = torch.empty(2 + 3 * R, dtype=torch.float32, device=logits.device)
+    _lib.check(L.du_val_dice_bce(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, R, HW, u, _p(ws), n, _st()), "du_val_dice_bce")
+    mult = _dice_group(sums, group, "dice_sums")
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    coef = torch.empty(2 * R + 1, dtype=torch.float32, device=logits.device)
+    _lib.check(L.du_dice_bce_finish(_p(sums), _p(loss), _p(coef), R, u, float(smooth), mult, _st()), "du_dice_bce_finish")
+    return loss.view(()), counts
 
 
 # ----------------------------------------------------------------------------------------------------

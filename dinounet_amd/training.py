@@ -2,7 +2,8 @@
 (dinounet/training/nnUNetTrainer/nnUNetTrainer.py:899-929): forward -> DC+CE loss -> backward -> clip_grad_norm_(12)
 -> SGD(nesterov, momentum 0.99, wd 3e-5).  On the GPU the loss is the fused Dice+CE kernel pair (csrc/loss.hip) and clip + SGD the
 fused three-launch optimiser (csrc/optim.hip); the torch formula below serves the CPU / many-class path of the gloo tests.
-build_loss covers the trainer's other label configurations (ignore label, regions: nnUNetTrainer.py:355-365)."""
+build_loss covers the trainer's other label configurations (ignore label, regions: nnUNetTrainer.py:355-365); ValStep / validation_counts
+are the validation half of the epoch (validation_step / on_validation_epoch_end, nnUNetTrainer.py:946-1052)."""
 import os
 import threading
 
@@ -482,3 +483,230 @@ class TrainStep:
             self.opt.refresh_hyper()                        # the captured step re-reads lr & co. from the pinned host buffer
         self.graph.replay()
         return self.loss
+
+
+def _cpu_validation_counts(logits, target, regions=None, ignore_label=None):
+    """nnUNetTrainer.validation_step, nnUNetTrainer.py:971-994 with get_tp_fp_fn_tn (dice.py:122-167), restated in integer torch ops:
+    (3, C) int64 = [tp | fp | fn] over axes (0, 2, 3).  The oracle of the HIP counts (tests) and the CPU path."""
+    if regions is not None:
+        onehot = labels_to_regions(target, regions, ignore_label)
+        R = len(regions)
+        pred = torch.sigmoid(logits.float()) > 0.5                                          # :973-974
+        y = onehot[:, :R].bool()
+        m = (onehot[:, R:] == 0) if ignore_label is not None else torch.ones_like(y[:, :1])  # :987-990
+    else:
+        lab = target[:, :1].long()
+        pred = torch.zeros(logits.shape, dtype=torch.bool, device=logits.device).scatter_(1, logits.argmax(1)[:, None], True)   # :976-979
+        if ignore_label is not None:
+            m = lab != ignore_label                                                         # :984
+            lab = torch.where(m, lab, torch.zeros_like(lab))                                # :986
+        else:
+            m = torch.ones_like(lab, dtype=torch.bool)
+        y = torch.zeros(logits.shape, dtype=torch.bool, device=logits.device).scatter_(1, lab, True)
+    tp = (pred & y & m).sum((0, 2, 3))
+    fp = (pred & ~y & m).sum((0, 2, 3))
+    fn = (~pred & y & m).sum((0, 2, 3))
+    return torch.stack([tp, fp, fn]).to(torch.int64)
+
+
+def _val_loss_counts(logits, target, mode, regions, ignore_label, table, smooth, ddp, group, counts=None, accum=None):
+    """validation loss (the training loss's forward value) and this step's (3, C) counts; `accum` += counts.  GPU: one fused pass
+    (ops.val_dice_ce / ops.val_dice_bce); CPU, or more classes than the kernels serve: the torch formulas."""
+    C_ = logits.shape[1]
+    fused = logits.is_cuda and ((1 <= C_ <= 8) if mode == "regions" else (2 <= C_ <= 8))
+    if ddp is None:
+        ddp = _ddp_default(group)
+    if fused:
+        from . import ops
+        g = (group if group is not None else dist.group.WORLD) if ddp else None
+        if mode == "regions":
+            onehot = labels_to_regions(target, regions, ignore_label, table=table)
+            return ops.val_dice_bce(logits, onehot, ignore_label is not None, smooth, g, counts, accum)
+        return ops.val_dice_ce(logits, target, ignore_label, smooth, g, counts, accum)
+    with torch.no_grad():
+        if mode == "regions":
+            onehot = labels_to_regions(target, regions, ignore_label, table=table)
+            loss = dc_and_bce_loss(logits, onehot, ignore_label is not None, smooth, ddp=ddp, group=group)
+        else:
+            loss = dc_and_ce_loss(logits, target, smooth, ddp=ddp, group=group, ignore_label=ignore_label)
+        c = _cpu_validation_counts(logits, target, regions, ignore_label)
+        if counts is None:
+            counts = c
+        else:
+            counts.copy_(c)
+        if accum is not None:
+            accum += c
+    return loss.detach(), counts
+
+
+def validation_counts(logits, target, regions=None, ignore_label=None):
+    """tp, fp, fn of nnUNetTrainer.validation_step (nnUNetTrainer.py:971-994): int64 tensors of length K (softmax modes: the argmax
+    prediction, lowest index among equal maxima; every class, the background included) or R (regions: sigmoid(x) > 0.5).  target (B,1,H,W)
+    integer labels in every mode (regions: converted by labels_to_regions, as SegLoss does); a pixel with `ignore_label` adds to no count.
+    On the GPU the HIP validation pass (csrc/loss.hip, which predicts a region where x > 0: the same predicate outside 0 < x < ~1.2e-7,
+    where torch's fp32 sigmoid rounds to exactly 0.5); on the CPU the plain torch restatement."""
+    C_ = logits.shape[1]
+    if logits.is_cuda:
+        if regions is not None and len(regions) != C_:
+            raise ValueError(f"validation_counts: {C_} logits planes, {len(regions)} regions")
+        mode = "regions" if regions is not None else ("softmax_ignore" if ignore_label is not None else "softmax")
+        _, c = _val_loss_counts(logits, target, mode, regions, ignore_label, None, 1e-5, False, None)
+    else:
+        c = _cpu_validation_counts(logits, target, regions, ignore_label)
+    return c[0], c[1], c[2]
+
+
+class ValStep:
+    """One validation step of the reference trainer (nnUNetTrainer.validation_step, nnUNetTrainer.py:946-1008) on static input buffers,
+    the eval-mode sibling of TrainStep:  net.eval() -> no_grad forward -> fused loss + tp / fp / fn (csrc/loss.hip, one pass over the
+    logits); net.train(...) is restored on exit.  Nothing is read back per step: every step adds its counts to `counts` ((3, C) int64 =
+    [tp | fp | fn], all classes), its loss to `loss_sum` (float64) -- both on the device -- and 1 to `steps`.  last() returns the
+    reference's per-step dict, epoch_end() what on_validation_epoch_end (:1010-1052) logs.
+
+    With `graph=True` the step is captured once into a hipGraph after `warmup` eager steps and replayed.  The graph reads the parameters
+    and running statistics in place, so it stays valid while a TrainStep on the same `net` updates them (not if they are re-allocated:
+    build a new ValStep then; inference.clear_window_cache states the same rule).  `loss`: a build_loss module or None (plain labels);
+    mode, regions, ignore label, smooth, ddp and group come from it, the region table was built with it, outside any capture.  With a
+    group the Dice sums are all-reduced as in the training forward (the reference's validation loss is the same module); under a
+    capture that all-reduce is recorded into the graph, a capture that fails falls back to eager steps with a warning, and the multi-rank
+    capture itself has been run on CPU / gloo eager steps only, not on several GPUs."""
+
+    def __init__(self, net, x_shape, tgt_shape, device, loss=None, graph=True, warmup=2):
+        self.net = net
+        device = torch.device(device)
+        self.mode = "softmax" if loss is None else loss.mode
+        self.regions = None if loss is None else loss.regions
+        self.ignore_label = None if loss is None else loss.ignore_label
+        self.smooth = 1e-5 if loss is None else loss.smooth
+        self.ddp = None if loss is None else loss.ddp
+        self.group = None if loss is None else loss.group
+        self.table = None
+        if self.regions is not None and device.type == "cuda":
+            self.table = loss.table if loss.table.device == device else _region_table(self.regions, device)
+        self.x = torch.zeros(x_shape, device=device)
+        self.tgt = torch.zeros(tgt_shape, dtype=torch.long, device=device)
+        self.counts = None               # (3, C) int64, allocated at the first step (C = the network's output planes)
+        self.loss_sum = torch.zeros((), dtype=torch.float64, device=device)
+        self.steps = 0
+        self.loss = None                 # this step's loss (device scalar) and counts
+        self.step_counts = None
+        self.graph = None
+        self.use_graph = bool(graph) and device.type == "cuda"
+        self.warmup = max(1, warmup)     # the first step allocates the accumulators: never inside the capture
+        self._n = 0
+
+    def _step(self):
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            with torch.no_grad():
+                logits = self.net(self.x)
+                if isinstance(logits, (list, tuple)):
+                    logits = logits[0]
+                if self.counts is None:
+                    C_ = logits.shape[1]
+                    self.counts = torch.zeros((3, C_), dtype=torch.int64, device=self.x.device)
+                    self.step_counts = torch.zeros((3, C_), dtype=torch.int64, device=self.x.device)
+                loss, _ = _val_loss_counts(logits, self.tgt, self.mode, self.regions, self.ignore_label, self.table, self.smooth,
+                                           self.ddp, self.group, counts=self.step_counts, accum=self.counts)
+                self.loss_sum += loss.double()
+        finally:
+            self.net.train(was_training)
+        return loss
+
+    def __call__(self, x=None, tgt=None):
+        if x is not None:
+            self.x.copy_(x, non_blocking=True)
+        if tgt is not None:
+            self.tgt.copy_(tgt, non_blocking=True)
+        self.loss = self._run()
+        self.steps += 1                                # counted once the step has been issued
+        return self.loss
+
+    def _run(self):
+        if not self.use_graph:
+            return self._step()
+        if self.graph is None:
+            if self._n < self.warmup:                  # eager warm-up on a side stream (allocator + lazy caches settle); real steps
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    loss = self._step()
+                torch.cuda.current_stream().wait_stream(s)
+                self._n += 1
+                return loss
+            torch.cuda.synchronize()
+            from . import ops
+            pg = dist.is_available() and dist.is_initialized()
+            if pg and dist.get_backend() == "nccl":
+                import time
+                time.sleep(0.35)                       # RCCL's watchdog retires the warm-up steps' work before the capture (see TrainStep)
+            # (thread_local: with a process group alive its watchdog thread polls events while this thread captures, see TrainStep)
+            mode = "thread_local" if pg else "global"
+            graph = torch.cuda.CUDAGraph()
+            try:
+                # a capture records, it does not run: a failure leaves the accumulators untouched
+                with ops.capture(graph, capture_error_mode=mode):     # ks_scratch_prepare on the capture stream first
+                    self.loss = self._step()
+                self.graph = graph
+            except Exception as e:  # noqa: BLE001
+                # capture is an optimisation: a step that cannot be captured still has to validate.  With a Dice group the all-reduce
+                # is recorded into the graph (no segmented capture here); that multi-rank capture has not been exercised on hardware
+                import warnings
+                warnings.warn(f"hipGraph capture of the validation step failed ({e!r}); continuing with eager steps")
+                torch.cuda.synchronize()
+                self.use_graph = False
+                return self._step()
+        self.graph.replay()
+        return self.loss
+
+    def _drop_bg(self, a):
+        return a if self.mode == "regions" else a[1:]
+
+    def last(self):
+        """the reference's validation_step return value for the latest step (:996-1008; syncs): loss and tp_hard / fp_hard / fn_hard as
+        numpy arrays, the background class dropped in the softmax modes"""
+        c = self.step_counts.cpu().numpy()
+        return {"loss": self.loss.detach().cpu().numpy(), "tp_hard": self._drop_bg(c[0]), "fp_hard": self._drop_bg(c[1]),
+                "fn_hard": self._drop_bg(c[2])}
+
+    def reset(self):
+        if self.counts is not None:
+            self.counts.zero_()
+        self.loss_sum.zero_()
+        self.steps = 0
+
+    def absorb(self, other):
+        """continue the epoch another ValStep began (another batch shape, e.g. a ragged last batch): its accumulators are added to
+        this one's and zeroed.  Same device, same number of classes."""
+        if other.counts is not None:
+            if self.counts is None:
+                self.counts = torch.zeros_like(other.counts)
+                self.step_counts = torch.zeros_like(other.counts)
+            self.counts += other.counts
+        self.loss_sum += other.loss_sum
+        self.steps += other.steps
+        other.reset()
+
+    def epoch_end(self, group=None):
+        """on_validation_epoch_end (:1010-1052; syncs): with a group the counts, the loss sum and the step count are all-reduced (SUM).
+        Dice = 2 tp / (2 tp + fp + fn) in float64 per foreground class / region, nan where tp = fp = fn = 0; mean_fg_dice = nanmean.
+        Zeroes the accumulators."""
+        import numpy as np
+        if self.counts is None:
+            raise RuntimeError("ValStep.epoch_end: no step has run")
+        counts, tail = self.counts.clone(), torch.stack([self.loss_sum, torch.tensor(float(self.steps), dtype=torch.float64,
+                                                                                    device=self.loss_sum.device)])
+        if group is not None and dist.is_available() and dist.is_initialized():
+            dist.all_reduce(counts, group=group)
+            dist.all_reduce(tail, group=group)
+        c = counts.cpu().numpy()
+        tail = tail.cpu().numpy()
+        steps = int(round(float(tail[1])))
+        tp, fp, fn = (self._drop_bg(c[i]) for i in range(3))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dice = 2.0 * tp.astype(np.float64) / (2.0 * tp + fp + fn).astype(np.float64)
+            mean_fg = float(np.nanmean(dice)) if np.isfinite(dice).any() else float("nan")
+        self.reset()
+        return {"val_loss": float(tail[0]) / steps if steps else float("nan"), "dice_per_class_or_region": [float(d) for d in dice],
+                "mean_fg_dice": mean_fg, "tp": tp, "fp": fp, "fn": fn, "steps": steps}

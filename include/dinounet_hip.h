@@ -440,6 +440,23 @@ int du_dice_bce_bwd(const float* logits, const uint8_t* target, const float* coe
 int du_labels_to_regions(const int64_t* seg, const int64_t* table, uint8_t* out, int B, int R, int64_t HW, int has_ignore,
                          int64_t ignore_label, void* stream);
 
+/* ---- validation step (nnUNetTrainer.validation_step, nnUNetTrainer.py:946-1008 with get_tp_fp_fn_tn, dice.py:122-167): ONE read of the
+        logits gives the sums of the matching training loss above (same layout and the same bits: run the matching *_finish on them) and the
+        exact counts of the hard prediction.  counts (3, C) int64 = this step's [tp | fp | fn] over all C = K classes / R regions; accum
+        (3, C) int64 += counts (NULL: none).  Prediction: argmax over K, lowest index among equal maxima (softmax modes); x > 0 (regions: the
+        reference's sigmoid(x) > 0.5 except for 0 < x < ~1.2e-7, where torch's fp32 sigmoid rounds to 0.5).  Finite logits.  A pixel with the
+        ignore label / ignore plane set adds to no count.  Integer arithmetic throughout, two stages, fixed order.  ws: *_ws_elems 4-byte
+        elements.  DU_ERR_UNSUPPORTED for K outside [2,8], R outside [1,8] or B * HW >= 2^31 (int32 block partials). ---- */
+int64_t du_val_dice_ce_ws_elems(int B, int K, int64_t HW);
+int du_val_dice_ce(const float* logits, const int64_t* target, float* sums, int64_t* counts, int64_t* accum, int B, int K, int64_t HW,
+                   float* ws, int64_t ws_elems, void* stream);
+int64_t du_val_dice_ce_masked_ws_elems(int B, int K, int64_t HW);
+int du_val_dice_ce_masked(const float* logits, const int64_t* target, float* sums, int64_t* counts, int64_t* accum, int B, int K,
+                          int64_t HW, int64_t ignore_label, float* ws, int64_t ws_elems, void* stream);
+int64_t du_val_dice_bce_ws_elems(int B, int R, int64_t HW);
+int du_val_dice_bce(const float* logits, const uint8_t* target, float* sums, int64_t* counts, int64_t* accum, int B, int R, int64_t HW,
+                    int has_ignore, float* ws, int64_t ws_elems, void* stream);
+
 /* ---- FAPM FiLM modulation (dinounet_training.py:427-429): z = gamma * z_specific + beta; gb (rows,2R) = [gamma|beta], z2 (rows,2R) =
         [z_shared|z_specific], z (rows,R).  Backward writes all of dgb and the z_specific half of dz2. ---- */
 int du_film_fwd(int dtype, const void* gb, const void* z2, void* z, int64_t rows, int R, void* stream);
