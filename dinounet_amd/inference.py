@@ -14,6 +14,9 @@ two indexed read-modify-write torch ops per window.  Test-time mirroring (predic
 averaged with the un-flipped predictions of every non-empty combination of the allowed mirror axes) is available through
 mirror_axes=...; the in-trainer validation passes use_mirroring=False (nnUNetTrainer.py:1160), the stand-alone predictor defaults to
 the checkpoint's inference_allowed_mirroring_axes.  There is no CPU path: the module needs the GPU.
+What follows the logits in the reference (resampling, argmax / region paint, bbox paste, per-case metrics; export_prediction.py:15-68,
+evaluate_predictions.py:152-234) is export.py: predict_segmentation runs the window loop below and goes from the accumulators straight
+to the label map.
 `acvl_utils.pad_nd_image` (not vendored in the reference tree) is restated from its published behaviour: centred constant padding
 up to the patch size, extra pixel on the high side."""
 import itertools
@@ -127,12 +130,10 @@ def _mirror_and_predict(forward, x, combos):
 
 
 @torch.no_grad()
-def predict_sliding_window_logits(net, data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
-                                  mirror_axes=None):
-    """data (C, D, H, W) on the GPU (or host: moved once) -> fp32 logits (K, D, H, W) on the GPU.
-    predict_from_raw_data.py:680-727 with _internal_predict_sliding_window_return_logits :571-621.  graph=True replays a captured
-    forward of a full window batch (worth it from a few batches per volume on).  mirror_axes: allowed_mirroring_axes of the
-    predictor (for this 2D path a subset of (0, 1) = the window's rows / columns), None = no test-time mirroring."""
+def _accumulate_windows(net, data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes):
+    """The window loop shared by predict_sliding_window_logits and export.predict_segmentation: data (C, D, H, W) -> the accumulators
+    predicted_logits (K, D, Hp, Wp) and n_predictions (D, Hp, Wp) of the padded volume (predict_from_raw_data.py:607-608, not yet
+    divided) and the (y, x) slices that undo the padding."""
     assert data.ndim == 4, "input_image must be a 4D tensor (c, d, y, x)"
     dev = next(net.parameters()).device
     if dev.type != "cuda":
@@ -183,9 +184,26 @@ def predict_sliding_window_logits(net, data, patch_size, tile_step_size=0.5, use
             coords = coords_all[i0:i0 + len(chunk)]
             _lib.check(L.du_window_accumulate(logits.data_ptr(), gauss.data_ptr(), coords.data_ptr(), pred.data_ptr(), npred.data_ptr(),
                                               len(chunk), K, ph, pw, D, H, W, st), "du_window_accumulate")
-        _lib.check(L.du_window_normalize(pred.data_ptr(), npred.data_ptr(), K, D * H * W, st), "du_window_normalize")
-        if not math.isfinite(float(pred.abs().max())):
-            raise RuntimeError("Encountered inf in predicted array")                                 # :612-615
-        return pred[:, :, ys, xs]
+        return pred, npred, (ys, xs)
     finally:
         net.train(was_training)
+
+
+@torch.no_grad()
+def predict_sliding_window_logits(net, data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
+                                  mirror_axes=None):
+    """data (C, D, H, W) on the GPU (or host: moved once) -> fp32 logits (K, D, H, W) on the GPU.
+    predict_from_raw_data.py:680-727 with _internal_predict_sliding_window_return_logits :571-621.  graph=True replays a captured
+    forward of a full window batch (worth it from a few batches per volume on).  mirror_axes: allowed_mirroring_axes of the
+    predictor (for this 2D path a subset of (0, 1) = the window's rows / columns), None = no test-time mirroring."""
+    pred, npred, (ys, xs) = _accumulate_windows(net, data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes)
+    K = pred.shape[0]
+    _lib.check(_lib.lib().du_window_normalize(pred.data_ptr(), npred.data_ptr(), K, npred.numel(), torch.cuda.current_stream().cuda_stream),
+               "du_window_normalize")
+    if not math.isfinite(float(pred.abs().max())):
+        raise RuntimeError("Encountered inf in predicted array")                                 # :612-615
+    return pred[:, :, ys, xs]
+
+
+# the export tail (label maps, probabilities, per-case metrics) lives in export.py; its names are part of this module's interface
+from .export import case_metrics, logits_to_segmentation, predict_segmentation  # noqa: E402,F401

@@ -35,6 +35,9 @@
  *       <- the ignore-label and region configurations of nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365):
  *          DC_and_CE_loss(ignore_label) (compound_losses.py:31-56), DC_and_BCE_loss (compound_losses.py:83-99),
  *          ConvertSegmentationToRegionsTransform (nnUNetTrainer.py:766-767)
+ *   du_export_seg, du_seg_counts
+ *       <- convert_predicted_logits_to_segmentation_with_correct_shape (inference/export_prediction.py:15-68) and
+ *          compute_metrics' counts (evaluation/evaluate_predictions.py:75-94, 176-186)
  */
 #ifndef DINOUNET_HIP_H
 #define DINOUNET_HIP_H
@@ -561,6 +564,33 @@ int du_debug_attn_census(uint64_t* host, int n);
 int du_window_accumulate(const float* logits, const float* gauss, const int32_t* coords, float* pred, float* npred, int nb, int K,
                          int ph, int pw, int D, int H, int W, void* stream);
 int du_window_normalize(float* pred, const float* npred, int K, int64_t n, void* stream);
+
+/* ---- export tail: accumulators -> label map in the case's original geometry, in ONE pass
+   (convert_predicted_logits_to_segmentation_with_correct_shape, dinounet/inference/export_prediction.py:15-68, with
+   LabelManager.convert_probabilities_to_segmentation / revert_cropping_on_probabilities, utilities/label_handling/label_handling.py:143-175,
+   185-209).  sums (K, D, Hp, Wp) fp32 = the un-normalised predicted_logits of du_window_accumulate, npred (D, Hp, Wp) fp32 (NULL = 1:
+   finished logits); (y0, x0, Hc, Wc) the un-padding window inside (Hp, Wp); (Ho, Wo) = shape_after_cropping_and_before_resampling[1:];
+   (D0, H0, W0) = shape_before_cropping, (bd, by, bx) the low corner of bbox_used_for_cropping, whose size is (D, Ho, Wo).
+   seg (D0, H0, W0) uint8, written in full (0 outside the bbox); probs (K, D0, H0, W0) fp32 or NULL (outside the bbox: plane 0 = 1 in softmax
+   mode, all 0 in region mode).  mode DU_EXPORT_SOFTMAX (K in [2,8]): argmax, lowest index among equal maxima; DU_EXPORT_REGIONS (K = R in
+   [1,8]): byte i of region_order is regions_class_order[i], the label is that of the LARGEST i with logit_i > 0, else 0 (the overwrite
+   loop of label_handling.py:170-171; x > 0 for sigmoid(x) > 0.5 as in the validation step above).  (Ho, Wo) == (Hc, Wc): the raw sums are
+   compared, no arithmetic.  Otherwise order-1 interpolation of sums / npred at 4 taps, edge clamp, source position from integers:
+   n = (2 dst + 1) Hc - Ho, tap floor(n / 2 Ho), weight (n mod 2 Ho) / (2 Ho).  Slices are independent.  flag (DEVICE int32, zeroed by the
+   caller) = 1 if a sums / npred element read for a voxel inside the window is not finite (predict_from_raw_data.py:612-615).
+   DU_ERR_UNSUPPORTED: K out of range; DU_ERR_BAD_ARG: window outside (Hp, Wp), bbox outside (D0, H0, W0). */
+#define DU_EXPORT_SOFTMAX 0
+#define DU_EXPORT_REGIONS 1
+int du_export_seg(const float* sums, const float* npred, uint8_t* seg, float* probs, int32_t* flag, int K, int D, int Hp, int Wp, int y0,
+                  int x0, int Hc, int Wc, int Ho, int Wo, int D0, int H0, int W0, int bd, int by, int bx, int mode, int64_t region_order,
+                  void* stream);
+/* per-case counts (compute_tp_fp_fn_tn with region_or_label_to_mask, dinounet/evaluation/evaluate_predictions.py:75-94, 176-186): pred,
+   ref (n) uint8 label maps, masks (R) int64 DEVICE bit masks as in du_labels_to_regions (labels 0..63, any other label is in no region),
+   counts (4, R) int64 = tp | fp | fn | tn over the voxels with ref != ignore_label (has_ignore).  Integers, two stages, fixed order.
+   ws: du_seg_counts_ws_elems int32 elements.  DU_ERR_UNSUPPORTED for R outside [1,8] or n >= 2^31. */
+int64_t du_seg_counts_ws_elems(int64_t n, int R);
+int du_seg_counts(const uint8_t* pred, const uint8_t* ref, const int64_t* masks, int64_t* counts, int64_t n, int R, int has_ignore,
+                  int ignore_label, int32_t* ws, int64_t ws_elems, void* stream);
 
 /* ---- fused clip_grad_norm_ + Nesterov SGD over all trainable tensors (replaces
    torch.nn.utils.clip_grad_norm_(params, 12) + torch.optim.SGD.step(), dinounet/training/nnUNetTrainer/nnUNetTrainer.py:486,922-924).
