@@ -48,7 +48,7 @@ class TnJob(C.Structure):
                 ("taps", C.c_int32), ("inner", C.c_int32), ("inner_total", C.c_int32), ("c_off", C.c_int32)]
 
 
-_CTYPE = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "int32_t": C.c_int32}
+_CTYPE = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "int32_t": C.c_int32, "double": C.c_double}
 
 
 def header_prototypes(path=HEADER):

@@ -13,10 +13,19 @@ resampling they exist at four taps per output pixel only.  One uint8 volume cros
 are a second integer kernel (du_seg_counts).  CPU tensors take a torch restatement that interpolates in float64 with the same integer
 source positions; it is what the tests compare the kernel against.
 
+The surface metrics of that table, HD95 and ASD (compute_surface_distances, evaluate_predictions.py:97-149: medpy.metric.hd95 / asd),
+are computed on the device as well (csrc/surface.hip): the border voxels of every label or region of both maps, an exact separable
+Euclidean distance transform of the complement of each border set in squared fp64 distances, and its values at the other map's border
+voxels compacted per region and direction.  Only two order statistics and one sum per region cross to the host.  CPU tensors take the
+medpy formula written with scipy.ndimage and numpy.percentile.
+
 Differences from the reference, on purpose: a region is predicted where logit > 0 (the reference: torch's fp32 sigmoid(x) > 0.5; they
 differ only for 0 < x < ~1.2e-7); the resampling is in-plane only (shape_after_cropping_and_before_resampling[0] must
-be the number of slices); label maps are uint8 (at most 254 foreground labels; the reference switches to uint16 at 255, :46); HD95 / ASD
-(medpy surface metrics) are not computed."""
+be the number of slices); label maps are uint8 (at most 254 foreground labels; the reference switches to uint16 at 255, :46); the surface
+metrics need a spacing of three positive floats (the reference's "pad or trim the spacing" branches are not mirrored) and volumes of at most
+1024 voxels per axis."""
+import math
+
 import torch
 
 from . import _lib
@@ -257,11 +266,14 @@ def segmentation_counts(seg_pred, seg_ref, labels_or_regions, ignore_label=None)
     return _counts_torch(seg_pred, seg_ref, masks, ignore_label)
 
 
-def case_metrics(seg_pred, seg_ref, labels_or_regions, ignore_label=None):
+def case_metrics(seg_pred, seg_ref, labels_or_regions, ignore_label=None, spacing=None):
     """The `metrics` dict of compute_metrics (evaluate_predictions.py:176-234) for one case: per label or region (the key, as given; lists
     become tuples) Dice, IoU, Sensitivity, Specificity, Precision, FP, TP, FN, TN, n_pred, n_ref with the nan rules of :189-210.  The
-    counts are exact integers from the device; the ratios are float64 on the host.  HD95 / ASD are not computed."""
+    counts are exact integers from the device; the ratios are float64 on the host.  With `spacing` (three positive floats in the axis
+    order of the (D, H, W) maps) HD95 and ASD of surface_metrics follow Precision, where the reference puts them (:225-226); the ignore
+    label plays no part in them."""
     counts = segmentation_counts(seg_pred, seg_ref, labels_or_regions, ignore_label).tolist()
+    surface = None if spacing is None else surface_metrics(seg_pred, seg_ref, labels_or_regions, spacing)
     nan = float("nan")
     metrics = {}
     for i, r in enumerate(labels_or_regions):
@@ -272,7 +284,202 @@ def case_metrics(seg_pred, seg_ref, labels_or_regions, ignore_label=None):
         m["Sensitivity"] = tp / (tp + fn) if tp + fn > 0 else nan                     # :197-200
         m["Specificity"] = tn / (tn + fp) if tn + fp > 0 else nan                     # :202-205
         m["Precision"] = tp / (tp + fp) if tp + fp > 0 else nan                       # :207-210
+        if surface is not None:
+            sm = surface[tuple(r) if isinstance(r, list) else r]
+            m["HD95"], m["ASD"] = sm["HD95"], sm["ASD"]                                # :225-226
         m["FP"], m["TP"], m["FN"], m["TN"] = fp, tp, fn, tn                           # :229-232
         m["n_pred"], m["n_ref"] = fp + tp, fn + tp                                    # :233-234
         metrics[tuple(r) if isinstance(r, list) else r] = m
     return metrics
+
+
+# ------------------------------------------------------------------------------------------------ surface metrics: HD95 / ASD
+SURFACE_MAX_EXTENT = 1024           # csrc/surface.hip: indices and offsets are 10-bit fields
+
+
+def _check_spacing(spacing):
+    try:
+        sp = tuple(float(v) for v in spacing)
+    except TypeError:
+        raise ValueError("spacing must be three positive floats in array-axis order") from None
+    if len(sp) != 3 or not all(math.isfinite(v) and 0.0 < v < 1e100 for v in sp):
+        raise ValueError(f"spacing must be three positive floats in array-axis order, got {spacing}")
+    return sp
+
+
+def _check_volume(seg):
+    if seg.ndim != 3:
+        raise ValueError("label maps must be (D, H, W); a 2-D case has D == 1")
+    if seg.is_cuda and any(int(e) > SURFACE_MAX_EXTENT for e in seg.shape):
+        raise ValueError(f"surface metrics on the device support at most {SURFACE_MAX_EXTENT} voxels per axis, got {tuple(seg.shape)}")
+
+
+def _mask_numpy(seg, bits):
+    """region_or_label_to_mask (evaluate_predictions.py:75-82) with the bit-mask convention of _region_mask_bits"""
+    import numpy as np
+    return np.isin(seg, [l for l in range(64) if (bits >> l) & 1])
+
+
+def _border_numpy(mask):
+    """medpy.metric.binary.__surface_distances: mask ^ binary_erosion(mask, generate_binary_structure(ndim, 1)) (border_value 0)"""
+    from scipy import ndimage
+    return mask ^ ndimage.binary_erosion(mask, structure=ndimage.generate_binary_structure(mask.ndim, 1), iterations=1)
+
+
+def _dist_sq_numpy(border, spacing):
+    """distance_transform_edt(~border, sampling=spacing) ** 2 without the root: the squared offsets to scipy's nearest border voxel, times
+    the spacing, squared and added in axis order -- the arithmetic scipy itself does before its sqrt.  inf without a border voxel."""
+    import numpy as np
+    from scipy import ndimage
+    if not border.any():
+        return np.full(border.shape, np.inf)
+    idx = ndimage.distance_transform_edt(~border, sampling=spacing, return_distances=False, return_indices=True)
+    d2 = np.zeros(border.shape, dtype=np.float64)
+    for ax in range(border.ndim):
+        off = (idx[ax] - np.arange(border.shape[ax]).reshape([-1 if a == ax else 1 for a in range(border.ndim)])).astype(np.float64)
+        off *= spacing[ax]
+        d2 += off * off
+    return d2
+
+
+def _surface_scipy(pred, ref, bits, spacing):
+    """medpy.metric.hd95(pred, ref, spacing) and medpy.metric.asd(pred, ref, spacing) for one region, restated from their published
+    behaviour: hd95 = percentile(hstack((d_pr, d_rp)), 95), asd = d_pr.mean(), d_pr = the distance field of ref's border at pred's border."""
+    import numpy as np
+    from scipy import ndimage
+    mp, mr = _mask_numpy(pred, bits), _mask_numpy(ref, bits)
+    bp, br = _border_numpy(mp), _border_numpy(mr)
+    out = {"HD95": float("nan"), "ASD": float("nan"), "n_surface_pred": int(bp.sum()), "n_surface_ref": int(br.sum())}
+    if not mp.any() or not mr.any():                                                  # evaluate_predictions.py:117-118
+        return out
+    d_pr = ndimage.distance_transform_edt(~br, sampling=spacing)[bp]
+    d_rp = ndimage.distance_transform_edt(~bp, sampling=spacing)[br]
+    out["HD95"] = float(np.percentile(np.hstack((d_pr, d_rp)), 95))
+    out["ASD"] = float(d_pr.mean())
+    return out
+
+
+def _lerp(a, b, t):
+    """numpy's _lerp (lib/_function_base_impl.py), the interpolation of numpy.percentile(method='linear')"""
+    d = b - a
+    return b - d * (1 - t) if t >= 0.5 else a + d * t
+
+
+def _surface_border_hip(pred, ref, chunk):
+    """-> bits (D, H, W) int16 view of the uint16 border bit sets, counts (4, R) int64 on the device"""
+    L = _lib.lib()
+    D, H, W = (int(i) for i in pred.shape)
+    dev, R = pred.device, len(chunk)
+    st = torch.cuda.current_stream().cuda_stream
+    table = torch.tensor([_signed64(m) for m in chunk], dtype=torch.int64).to(dev)
+    bits = torch.empty((D, H, W), dtype=torch.int16, device=dev)
+    counts = torch.empty((4, R), dtype=torch.int64, device=dev)
+    ws_elems = int(L.du_surface_border_ws_elems(D * H * W, R))
+    ws = torch.empty(max(ws_elems, 1), dtype=torch.int32, device=dev)
+    _lib.check(L.du_surface_border(pred.data_ptr(), ref.data_ptr(), table.data_ptr(), bits.data_ptr(), counts.data_ptr(), D, H, W, R,
+                                   ws.data_ptr(), ws_elems, st), "du_surface_border")
+    return bits, counts
+
+
+def _surface_ws(shape, dev):
+    D, H, W = (int(i) for i in shape)
+    ws_elems = int(_lib.lib().du_surface_ws_elems(D, H, W))
+    return torch.empty(max(ws_elems, 1), dtype=torch.float64, device=dev), ws_elems
+
+
+def _surface_hip(pred, ref, masks, spacing):
+    import ctypes
+    L = _lib.lib()
+    D, H, W = (int(i) for i in pred.shape)
+    dev = pred.device
+    st = torch.cuda.current_stream().cuda_stream
+    ws, ws_elems = _surface_ws(pred.shape, dev)
+    out = []
+    for i0 in range(0, len(masks), MAX_CLASSES):
+        chunk = masks[i0:i0 + MAX_CLASSES]
+        R = len(chunk)
+        bits, counts = _surface_border_hip(pred, ref, chunk)
+        n_pred, n_ref, nb_pred, nb_ref = counts.tolist()                              # synchronisation 1 of 2: segment sizes
+        active = [r for r in range(R) if n_pred[r] > 0 and n_ref[r] > 0]
+        rows = [{"HD95": float("nan"), "ASD": float("nan"), "n_surface_pred": nb_pred[r], "n_surface_ref": nb_ref[r]} for r in range(R)]
+        out.extend(rows)
+        if not active:
+            continue
+        off = [0]
+        for r in range(R):
+            on = r in active
+            off.append(off[-1] + (nb_pred[r] if on else 0))
+            off.append(off[-1] + (nb_ref[r] if on else 0))
+        seg_off = (ctypes.c_int64 * (2 * R + 1))(*off)
+        dist_sq = torch.empty(off[-1], dtype=torch.float64, device=dev)
+        sums = torch.zeros(R, dtype=torch.float64, device=dev)
+        _lib.check(L.du_surface_gather(bits.data_ptr(), D, H, W, R, sum(1 << r for r in active), spacing[0], spacing[1], spacing[2],
+                                       ctypes.addressof(seg_off), dist_sq.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws_elems, st),
+                   "du_surface_gather")
+        # the two order statistics around numpy's virtual index 0.95 (n - 1) of hstack((d_pr, d_rp)): both segments of a region are adjacent
+        picks = []
+        for r in active:
+            n = off[2 * r + 2] - off[2 * r]
+            lo = math.floor((n - 1) * 0.95)
+            srt = torch.sort(dist_sq[off[2 * r]:off[2 * r + 2]]).values
+            picks.append(srt[torch.tensor([lo, min(lo + 1, n - 1)], device=dev)])
+        got = torch.cat(picks + [sums]).tolist()                                      # synchronisation 2 of 2
+        for j, r in enumerate(active):
+            n = off[2 * r + 2] - off[2 * r]
+            vi = (n - 1) * 0.95
+            a, b = math.sqrt(got[2 * j]), math.sqrt(got[2 * j + 1])
+            rows[r]["HD95"] = float(_lerp(a, b, vi - math.floor(vi)))
+            rows[r]["ASD"] = got[2 * len(active) + r] / nb_pred[r]
+    return out
+
+
+def _check_pair(seg_pred, seg_ref, labels_or_regions):
+    if seg_pred.dtype != torch.uint8 or seg_ref.dtype != torch.uint8:
+        raise ValueError("label maps must be uint8")
+    if seg_pred.shape != seg_ref.shape or seg_pred.device != seg_ref.device:
+        raise ValueError("prediction and reference must have one shape and device")
+    if seg_pred.numel() == 0 or len(labels_or_regions) == 0:
+        raise ValueError("empty label map or no labels")
+
+
+def surface_metrics(seg_pred, seg_ref, labels_or_regions, spacing):
+    """HD95 and ASD of compute_surface_distances (evaluate_predictions.py:97-149) for every label or region: {key: {"HD95", "ASD",
+    "n_surface_pred", "n_surface_ref"}}, keys as in case_metrics.  uint8 (D, H, W) label maps of one shape and device (2-D data: D == 1,
+    where every mask voxel is a border voxel, as in the reference); spacing: three positive floats in array-axis order.  Either mask empty:
+    both nan (:117-118).  HD95 = numpy.percentile(hstack((d_pr, d_rp)), 95), ASD = d_pr.mean() (prediction to reference only, as
+    medpy.metric.asd).  CUDA tensors run csrc/surface.hip, 8 regions per chunk and two synchronisations per chunk, at most 1024 voxels
+    per axis; CPU tensors the scipy restatement."""
+    _check_pair(seg_pred, seg_ref, labels_or_regions)
+    _check_volume(seg_pred)
+    sp = _check_spacing(spacing)
+    masks = [_region_mask_bits(r) for r in labels_or_regions]
+    if seg_pred.is_cuda:
+        rows = _surface_hip(seg_pred.contiguous(), seg_ref.contiguous(), masks, sp)
+    else:
+        p, g = seg_pred.numpy(), seg_ref.numpy()
+        rows = [_surface_scipy(p, g, m, sp) for m in masks]
+    return {(tuple(r) if isinstance(r, list) else r): row for r, row in zip(labels_or_regions, rows)}
+
+
+def border_distance_sq(seg, region_or_label, spacing):
+    """(border bool (D, H, W), dist_sq float64 (D, H, W)) on seg's device: the border voxels of one label or region of a uint8 label map
+    (mask voxels with a face neighbour outside the mask or the volume) and the squared Euclidean distance (dz sz)^2 + (dy sy)^2 + (dx sx)^2
+    of every voxel to the nearest of them, inf if there is none."""
+    if seg.dtype != torch.uint8:
+        raise ValueError("label maps must be uint8")
+    if seg.numel() == 0:
+        raise ValueError("empty label map")
+    _check_volume(seg)
+    sp = _check_spacing(spacing)
+    m = _region_mask_bits(region_or_label)
+    if not seg.is_cuda:
+        border = _border_numpy(_mask_numpy(seg.numpy(), m))
+        return torch.from_numpy(border), torch.from_numpy(_dist_sq_numpy(border, sp))
+    seg = seg.contiguous()
+    D, H, W = (int(i) for i in seg.shape)
+    bits, _ = _surface_border_hip(seg, seg, [m])
+    ws, ws_elems = _surface_ws(seg.shape, seg.device)
+    field = torch.empty((D, H, W), dtype=torch.float64, device=seg.device)
+    _lib.check(_lib.lib().du_surface_field(bits.data_ptr(), field.data_ptr(), D, H, W, 0, sp[0], sp[1], sp[2], ws.data_ptr(), ws_elems,
+                                           torch.cuda.current_stream().cuda_stream), "du_surface_field")
+    return (bits & 1).bool(), field

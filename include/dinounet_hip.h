@@ -38,6 +38,8 @@
  *   du_export_seg, du_seg_counts
  *       <- convert_predicted_logits_to_segmentation_with_correct_shape (inference/export_prediction.py:15-68) and
  *          compute_metrics' counts (evaluation/evaluate_predictions.py:75-94, 176-186)
+ *   du_surface_border, du_surface_field, du_surface_gather
+ *       <- compute_surface_distances (evaluation/evaluate_predictions.py:97-149): medpy.metric.hd95 / asd, restated
  */
 #ifndef DINOUNET_HIP_H
 #define DINOUNET_HIP_H
@@ -603,6 +605,30 @@ int du_seg_counts(const uint8_t* pred, const uint8_t* ref, const int64_t* masks,
 int64_t du_clip_sgd_ws_elems(int nblocks);
 int du_clip_sgd(const int64_t* table, const int64_t* bprefix, int n_tensors, int nblocks, const float* hyper, float* ws,
                 int64_t ws_elems, void* stream);
+
+/* ---- surface metrics: border voxels and the exact Euclidean distance transform of their complement (csrc/surface.hip; HD95 / ASD of
+   compute_surface_distances, evaluate_predictions.py:97-149, i.e. medpy.metric.hd95 / asd).  Volumes are (D, H, W), every extent in
+   [1, 1024] (DU_ERR_UNSUPPORTED beyond: offsets and indices are 10-bit fields); spacings (sz, sy, sx) positive, in array-axis order.
+   du_surface_border: pred / ref uint8 label maps, masks (R <= 8) int64 DEVICE bit masks as in du_seg_counts.  bits (D, H, W) uint16: bit r =
+   the voxel is a border voxel of region r of pred, bit 8 + r = of ref (a mask voxel with one of its six face neighbours outside the mask or
+   outside the volume).  counts (4, R) int64 DEVICE = mask voxels pred | mask voxels ref | border voxels pred | border voxels ref, exact.
+   ws: du_surface_border_ws_elems int32 elements.
+   du_surface_field: field (D, H, W) fp64 = the squared distance (dz sz)^2 + (dy sy)^2 + (dx sx)^2 (added in that order) to the nearest
+   voxel with bit `bit` of `bits`, +inf if there is none.
+   du_surface_gather: for every region r with bit r of `active`: the ref field at the pred border voxels -> dist_sq[seg_off[2r] ..
+   seg_off[2r + 1]) and sqrt_sums[r] = the sum of their square roots (fixed order, no float atomics); the pred field at the ref border voxels
+   -> dist_sq[seg_off[2r + 1] .. seg_off[2r + 2]).  seg_off: 2R + 1 int64 on the HOST (read during the call), from the border counts; the
+   order inside a segment is not defined.  dist_sq, sqrt_sums (R) fp64 DEVICE.
+   ws of both: du_surface_ws_elems(D, H, W) 8-byte elements, 8-byte aligned = ceil(n / 4) + ceil(n / 2) + H * ceil(W / c) + 8, n = D H W,
+   c = the largest power of two <= 64 with c * D * 4 <= 65536 (6 bytes per voxel: one uint16 and one uint32 field, whatever R is). ---- */
+int64_t du_surface_border_ws_elems(int64_t n, int R);
+int du_surface_border(const uint8_t* pred, const uint8_t* ref, const int64_t* masks, uint16_t* bits, int64_t* counts, int D, int H, int W,
+                      int R, int32_t* ws, int64_t ws_elems, void* stream);
+int64_t du_surface_ws_elems(int D, int H, int W);
+int du_surface_field(const uint16_t* bits, double* field, int D, int H, int W, int bit, double sz, double sy, double sx, void* ws,
+                     int64_t ws_elems, void* stream);
+int du_surface_gather(const uint16_t* bits, int D, int H, int W, int R, int active, double sz, double sy, double sx,
+                      const int64_t* seg_off_host, double* dist_sq, double* sqrt_sums, void* ws, int64_t ws_elems, void* stream);
 
 #ifdef __cplusplus
 }
