@@ -15,6 +15,7 @@
 // hides under the matrix pipe.
 #include "common.h"
 #include "gemm_params.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -291,39 +292,122 @@ int launch_dtype(const du_gemm_args& a, hipStream_t st) {
 
 bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-}  // namespace
-
-int du_gemm_bf16_fast(const du_gemm_args& a, hipStream_t st);   // gemm_bf16.hip
-int du_gemm_nt_p8(const du_gemm_args& a, hipStream_t st, int tail_rows = 0);       // gemm_p8.hip
-int du_gemm_ragged_rows(const du_gemm_args& a);                      // gemm_bf16.hip
-int64_t du_gemm_skinny_ws_elems(int N, int K);                      // gemm_skinny.hip
-
-int du_gemm_route_bf16(const du_gemm_args& a);                       // gemm_bf16.hip
-
-extern "C" int du_gemm_route(const du_gemm_args* pa) {
-  if (!pa) return DU_ERR_BAD_ARG;
-  static const bool generic = DU_GETENV("DU_GEMM_GENERIC") != nullptr;
-  return generic ? 0 : du_gemm_route_bf16(*pa);
+// the exact-fp32 / any-alignment engine above: bf16 or fp32 operands, fp32 results for fp32 operands
+int launch_generic(const du_gemm_args& a, hipStream_t st) {
+  if (a.dtype == DU_BF16) {
+    if (a.out_dtype == DU_BF16) return launch_dtype<bf16_t, bf16_t>(a, st);
+    return launch_dtype<bf16_t, float>(a, st);
+  }
+  return launch_dtype<float, float>(a, st);
 }
 
-extern "C" int64_t du_gemm_ws_elems(const du_gemm_args* pa) {
-  if (!pa) return 0;
-  static const bool generic = DU_GETENV("DU_GEMM_GENERIC") != nullptr;
-  if (generic) return 0;
-  return du_gemm_ragged_rows(*pa) > 0 ? du_gemm_skinny_ws_elems(pa->N, pa->K) : 0;
+// the last r rows of `a` as a product of their own; the head keeps the operands and M - r rows
+void split_rows(const du_gemm_args& a, int r, du_gemm_args& head, du_gemm_args& tail) {
+  const long m0 = a.M - r;
+  const long osz = a.out_dtype == DU_BF16 ? 2 : 4;
+  head = a;
+  head.M = (int)m0;
+  tail = a;
+  tail.M = r;
+  tail.A = (const char*)a.A + m0 * a.lda * 2;
+  tail.C = (char*)a.C + m0 * a.ldc * osz;
+  if (a.residual) tail.residual = (const char*)a.residual + m0 * a.ldr * osz;
+  if (a.row_scale) tail.row_scale = a.row_scale + m0 / a.rs_rows;
 }
 
-long du_gemm_ks_bytes_bf16(const du_gemm_args& a);              // gemm_bf16.hip
-extern "C" int64_t du_gemm_ks_ws_bytes(const du_gemm_args* pa) {
-  if (!pa) return 0;
-  static const bool generic = DU_GETENV("DU_GEMM_GENERIC") != nullptr;
-  return generic ? 0 : du_gemm_ks_bytes_bf16(*pa);
+// ---- the plan, step 1: which kernels run.  p.rc = DU_ERR_UNSUPPORTED where none does ----
+void plan_kernels(const du_gemm_args& a, bool generic_only, GemmPlan& p) {
+  p.rc = DU_OK;
+  auto multi_phase = [&](const du_gemm_args& head, int choice, int riding) {     // gemm_p8.hip NT kernels (2 + choice = 7 is the resident-weights kernel)
+    p.family = choice == 5 ? 8 : 2 + choice;
+    p.variant = choice;
+    p.gather = head.a_mode == DU_IM2COL_ROW;
+    if (riding) { p.tail_rows = riding; p.tail_form = DU_TAIL_RIDES; }
+  };
+  // stores and the gate that exist in the multi-phase kernels' epilogues only: those kernels or nothing (callers fall back to a plain
+  // product + du_msda_prep / du_qkv_rope_split / du_swiglu_pairs)
+  if (a.store_mode == DU_STORE_MSDA_PREP || a.store_mode == DU_STORE_QKV_HEADS || a.store_mode == DU_STORE_QKV_ROPE) {
+    p.rc = DU_ERR_UNSUPPORTED;
+    if (a.dtype != DU_BF16 || a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW || a.split_k > 1) return;
+    du_gemm_args head = a;
+    int r = 0;
+    if (a.store_mode == DU_STORE_QKV_HEADS) {      // head-major planes from the persistent kernel's drain: whole 256-row tiles, ragged rows in the same launch
+      r = du_gemm_ragged_rows(a);
+      head.M = a.M - r;
+      if (head.M % 256) return;
+    }
+    const int c = du_gemm_p8_choice(head);
+    if (c) { p.rc = DU_OK; multi_phase(head, c, r); }
+    return;
+  }
+  if (a.act == DU_ACT_SWIGLU) {
+    p.rc = DU_ERR_UNSUPPORTED;
+    if (a.dtype != DU_BF16 || a.N % 2) return;
+    int c = du_gemm_p8_choice(a);
+    if (!c && p8_legal(a)) c = 2;      // the narrow tile where the heuristic would have preferred another family
+    if (c) { p.rc = DU_OK; multi_phase(a, c, 0); }
+    return;
+  }
+  // the bf16 kernel families: 16-byte epilogue vectors
+  bool fast = a.dtype == DU_BF16 && !generic_only && a.N % 4 == 0 && a.ldc % 4 == 0 && aligned16(a.C) && a.c_batch_stride % 4 == 0;
+  if (a.bias && !aligned16(a.bias)) fast = false;
+  if (a.gamma && !aligned16(a.gamma)) fast = false;
+  if (a.residual && (a.ldr % 4 || !aligned16(a.residual))) fast = false;
+  if (a.store_mode == DU_STORE_PIXEL_SHUFFLE2 && a.ps_C % 4) fast = false;
+  if (!fast) {
+    if (!du_gemm_modes_served(a.a_mode, a.b_mode) || (a.dtype != DU_BF16 && a.out_dtype != DU_F32)) p.rc = DU_ERR_UNSUPPORTED;
+    return;       // family 0
+  }
+  if (a.a_mode == DU_PLAIN_COL && (a.b_mode == DU_PLAIN_COL || a.b_mode == DU_IM2COL_COL)) {     // weight gradients: the multi-phase kernel where it is legal
+    p.tn_splits = du_gemm_tn_p8_splits(a);
+    if (p.tn_splits) { p.family = 5; p.gather = a.b_mode == DU_IM2COL_COL; return; }
+  }
+  if (du_gemm_rk_serves(a)) {        // K <= 256, tall M: the streaming kernel (any M: rows past the last full block are masked)
+    p.family = 7; p.gather = a.a_mode == DU_IM2COL_ROW;
+    return;
+  }
+  // large contraction-contiguous products: the multi-phase kernels where they pay, else the 128 x 128 direct-to-LDS kernel
+  const int r = du_gemm_ragged_rows(a);
+  if (r > 0 && a.ws && a.ws_elems >= du_gemm_skinny_ws_elems(a.N, a.K)) {
+    // exact part on the tile kernels; the short ragged tail rides in a multi-phase kernel's launch (extra workgroups behind the tiles), or
+    // runs on the K-parallel skinny kernels (gemm_skinny.hip) behind it
+    // (forking the tail onto a side stream with event edges measured slower both times it was tried, inside the hipGraph: round 1 beside
+    // the 128 x 128 kernels 191.6 vs 194.0 slices/s; round 2 beside the multi-phase kernels, 8 KB-LDS tail form, 33.9 vs 33.2 ms per step)
+    du_gemm_args head, tail;
+    split_rows(a, r, head, tail);
+    const int c = du_gemm_p8_choice(head);
+    if (c && du_gemm_p8_tail_ok(a, r)) { multi_phase(head, c, r); return; }
+    if (c || du_gemm_glds_serves(head)) {
+      if (c) multi_phase(head, c, 0); else p.family = 2;
+      const int form = du_gemm_skinny_form(tail);
+      p.tail_rows = r;
+      p.tail_form = form ? form : DU_TAIL_TILE_ENGINE;
+      return;
+    }
+  }
+  const int c = du_gemm_p8_choice(a);
+  if (c) { multi_phase(a, c, 0); return; }
+  if (du_gemm_glds_serves(a)) { p.family = 2; return; }
+  if (du_gemm_modes_served(a.a_mode, a.b_mode)) p.family = 1; else p.rc = DU_ERR_UNSUPPORTED;
 }
 
-extern "C" int du_gemm(const du_gemm_args* pa, void* stream) {
-  if (!pa) return DU_ERR_BAD_ARG;
-  const du_gemm_args& a = *pa;
-  hipStream_t st = (hipStream_t)stream;
+// ---- step 2: the scratch the product wants (asked before any is passed: a.ws / a.ks_ws do not count) ----
+int64_t plan_ks_bytes(const du_gemm_args& a) {
+  if (a.dtype != DU_BF16 || a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW) return 0;
+  du_gemm_args head = a;
+  head.ks_ws = nullptr; head.ks_ws_bytes = 0;      // (the ragged-row rule must not depend on the scratch being asked about)
+  int r = a.M % 256;
+  if (r < 1 || r > 64 || !du_gemm_p8_tail_ok(a, r)) r = 0;
+  head.M = a.M - r;
+  const long pair = du_gemm_p8_ks_bytes(head);
+  // (the sliced units exist in the one-shot tile kernels' launches: choice 1 / 2)
+  const int c = r > 0 ? du_gemm_p8_choice(head) : 0;
+  const long tail = (c == 1 || c == 2) ? du_gemm_p8_tail_bytes(a) : 0;
+  return pair > tail ? pair : tail;
+}
+
+// ---- step 3: du_gemm's argument checks, in the order their codes take precedence; `family` is what step 1 chose ----
+int plan_check(const du_gemm_args& a, int family) {
   if (a.M <= 0 || a.N <= 0 || a.K <= 0) return DU_ERR_BAD_ARG;
   if (!a.A || !a.B || !a.C) return DU_ERR_BAD_ARG;
   const int vec = a.dtype == DU_BF16 ? 8 : 4;
@@ -349,56 +433,66 @@ extern "C" int du_gemm(const du_gemm_args* pa, void* stream) {
   // weight-gradient form (A contraction-major): row_scale scales the CONTRACTION rows (per-sample DropPath scale on dY); only the bf16
   // tile engine implements it, and only for K tiles that lie inside one sample
   const bool k_scale = a.row_scale && a.a_mode == DU_PLAIN_COL;
-  if (k_scale) {
-    const int route = a.dtype == DU_BF16 && !DU_GETENV("DU_GEMM_GENERIC") ? du_gemm_route_bf16(a) : 0;
-    if (route != 1 || a.rs_rows <= 0 || a.rs_rows % 64 || a.bias || a.act || a.gamma || a.residual || a.store_mode) return DU_ERR_UNSUPPORTED;
-  }
+  if (k_scale && (family != 1 || a.rs_rows <= 0 || a.rs_rows % 64 || a.bias || a.act || a.gamma || a.residual || a.store_mode)) return DU_ERR_UNSUPPORTED;
   if (a.split_k > 1 && (a.out_dtype != DU_F32 || a.bias || a.act || a.gamma || (a.row_scale && !k_scale) || a.residual ||
                         (a.store_mode && a.store_mode != DU_STORE_SLABS))) return DU_ERR_BAD_ARG;
-  if (a.store_mode == DU_STORE_SLABS) {        // one slab per K range instead of atomics: the bf16 tile engine's split-K epilogue only
-    if (a.split_k <= 1 || a.dtype != DU_BF16 || a.batch > 1 || du_gemm_route_bf16(a) != 1) return DU_ERR_UNSUPPORTED;
+  // one slab per K range instead of atomics: the bf16 tile engine's split-K epilogue only
+  if (a.store_mode == DU_STORE_SLABS && (a.split_k <= 1 || a.batch > 1 || family != 1)) return DU_ERR_UNSUPPORTED;
+  if (a.store_mode == DU_STORE_PIXEL_SHUFFLE2 && (a.ps_C <= 0 || a.N != 4 * a.ps_C || a.ps_H <= 0 || a.ps_W <= 0 || a.M % (a.ps_H * a.ps_W))) return DU_ERR_BAD_ARG;
+  // bias-gradient side sums (a_colsum; b_colsum: ConvT, from the gathered dY operand): only the bf16 weight-gradient kernels accumulate them
+  const bool wgrad = a.a_mode == DU_PLAIN_COL && (family == 1 || family == 5);
+  if (a.b_colsum && (!wgrad || a.b_mode != DU_IM2COL_COL || a.geom.C <= 0 || a.N % a.geom.C)) return DU_ERR_UNSUPPORTED;
+  if (a.a_colsum && !wgrad) return DU_ERR_UNSUPPORTED;
+  return DU_OK;
+}
+
+}  // namespace
+
+GemmPlan du_gemm_plan(const du_gemm_args& a) {
+  static const bool generic_only = DU_GETENV("DU_GEMM_GENERIC") != nullptr;   // debugging aid: force the generic kernel
+  GemmPlan p{};
+  plan_kernels(a, generic_only, p);
+  if (!generic_only) {
+    p.ws_elems = du_gemm_ragged_rows(a) > 0 ? du_gemm_skinny_ws_elems(a.N, a.K) : 0;
+    p.ks_ws_bytes = plan_ks_bytes(a);
   }
-  if (a.store_mode == DU_STORE_PIXEL_SHUFFLE2 && a.residual && a.ldc % 1) return DU_ERR_BAD_ARG;
-  if (a.store_mode == DU_STORE_PIXEL_SHUFFLE2 && (a.ps_C <= 0 || a.N != 4 * a.ps_C || a.M % (a.ps_H * a.ps_W))) return DU_ERR_BAD_ARG;
-  if (a.b_colsum) {                      // ConvT bias gradient from the gathered dY operand: bf16 weight-gradient kernels only
-    const int route = a.dtype == DU_BF16 && a.a_mode == DU_PLAIN_COL && a.b_mode == DU_IM2COL_COL && !DU_GETENV("DU_GEMM_GENERIC") ? du_gemm_route_bf16(a) : 0;
-    if ((route != 1 && route != 5) || a.geom.C <= 0 || a.N % a.geom.C) return DU_ERR_UNSUPPORTED;
+  const int rc = plan_check(a, p.family);
+  if (rc != DU_OK) p.rc = rc;
+  return p;
+}
+
+extern "C" int du_gemm_route(const du_gemm_args* pa) { return pa ? du_gemm_plan(*pa).family : DU_ERR_BAD_ARG; }
+extern "C" int64_t du_gemm_ws_elems(const du_gemm_args* pa) { return pa ? du_gemm_plan(*pa).ws_elems : 0; }
+extern "C" int64_t du_gemm_ks_ws_bytes(const du_gemm_args* pa) { return pa ? du_gemm_plan(*pa).ks_ws_bytes : 0; }
+
+extern "C" int du_gemm_plan_describe(const du_gemm_args* pa, int64_t* out, int n) {
+  if (!pa || !out || n < 9) return DU_ERR_BAD_ARG;
+  const GemmPlan p = du_gemm_plan(*pa);
+  const int64_t v[9] = {p.rc, p.family, p.variant, p.gather, p.tail_rows, p.tail_form, p.tn_splits, p.ws_elems, p.ks_ws_bytes};
+  for (int i = 0; i < 9; i++) out[i] = v[i];
+  return 9;
+}
+
+extern "C" int du_gemm(const du_gemm_args* pa, void* stream) {
+  if (!pa) return DU_ERR_BAD_ARG;
+  const GemmPlan p = du_gemm_plan(*pa);
+  if (p.rc != DU_OK) return p.rc;
+  hipStream_t st = (hipStream_t)stream;
+  du_gemm_args head = *pa, tail = *pa;
+  if (p.tail_rows) split_rows(*pa, p.tail_rows, head, tail);
+  int rc;
+  if (p.variant) rc = du_gemm_nt_p8(head, st, p.variant, p.tail_form == DU_TAIL_RIDES ? p.tail_rows : 0);
+  else switch (p.family) {
+    case 0: rc = launch_generic(head, st); break;
+    case 1: rc = du_gemm_bf16_tiles(head, st); break;
+    case 2: rc = du_gemm_nt_glds(head, st); break;
+    case 5: rc = du_gemm_tn_p8(head, st, p.tn_splits); break;
+    default: rc = du_gemm_nt_rk(head, st); break;      // 7
   }
-  if (a.a_colsum) {                      // bias-gradient side sum: only the bf16 weight-gradient kernels accumulate it
-    const int route = a.dtype == DU_BF16 && a.a_mode == DU_PLAIN_COL && !DU_GETENV("DU_GEMM_GENERIC") ? du_gemm_route_bf16(a) : 0;
-    if (route != 1 && route != 5) return DU_ERR_UNSUPPORTED;
+  if (rc != DU_OK) return rc;
+  switch (p.tail_form) {
+    case DU_TAIL_SKINNY_FUSED: case DU_TAIL_SKINNY_PAIR: return du_gemm_skinny(tail, st, p.tail_form);
+    case DU_TAIL_TILE_ENGINE: tail.ws = nullptr; tail.ws_elems = 0; return du_gemm_bf16_tiles(tail, st);
   }
-  if (a.store_mode == DU_STORE_MSDA_PREP) {      // sampling locations + attention weights from the 256 x 256 kernel's epilogue, or nothing
-    if (a.dtype != DU_BF16 || a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW || a.split_k > 1) return DU_ERR_UNSUPPORTED;
-    return du_gemm_nt_p8(a, st);
-  }
-  if (a.store_mode == DU_STORE_QKV_HEADS) {      // head-major qkv planes from the persistent kernel's drain (ragged rows in the same launch), or nothing
-    if (a.dtype != DU_BF16 || a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW || a.split_k > 1) return DU_ERR_UNSUPPORTED;
-    const int r = du_gemm_ragged_rows(a);
-    if (r > 0) {
-      du_gemm_args head = a;
-      head.M = a.M - r;
-      return du_gemm_nt_p8(head, st, r);
-    }
-    return a.M % 256 ? DU_ERR_UNSUPPORTED : du_gemm_nt_p8(a, st);
-  }
-  if (a.store_mode == DU_STORE_QKV_ROPE) {       // fused RoPE + head split: the 256 x 128 multi-phase kernel or nothing
-    if (a.dtype != DU_BF16 || a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW || a.split_k > 1) return DU_ERR_UNSUPPORTED;
-    return du_gemm_nt_p8(a, st);
-  }
-  if (a.act == DU_ACT_SWIGLU) {          // gated epilogue: multi-phase bf16 NT kernels only (callers fall back to du_swiglu_pairs)
-    if (a.dtype != DU_BF16 || a.N % 2) return DU_ERR_UNSUPPORTED;
-    return du_gemm_nt_p8(a, st);
-  }
-  if (a.dtype == DU_BF16) {
-    static const bool generic_only = DU_GETENV("DU_GEMM_GENERIC") != nullptr;   // debugging aid: force the generic kernel
-    if (!generic_only) {
-      int rc = du_gemm_bf16_fast(a, st);
-      if (rc != DU_ERR_UNSUPPORTED) return rc;
-    }
-    if (a.out_dtype == DU_BF16) return launch_dtype<bf16_t, bf16_t>(a, st);
-    return launch_dtype<bf16_t, float>(a, st);
-  }
-  if (a.out_dtype == DU_F32) return launch_dtype<float, float>(a, st);
-  return DU_ERR_UNSUPPORTED;
+  return rc;
 }

@@ -17,6 +17,7 @@
 //    panel hit the same L2.
 #include "common.h"
 #include "gemm_params.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -448,19 +449,18 @@ extern "C" int du_gemm_slab_count(int K, int split_k) {
   return (K + kps - 1) / kps;
 }
 
-int du_gemm_nt_glds(const du_gemm_args& a, hipStream_t st);   // gemm_glds.hip
-int du_gemm_skinny(const du_gemm_args& a, hipStream_t st);    // gemm_skinny.hip
-int64_t du_gemm_skinny_ws_elems(int N, int K);
+// the operand-mode pairs launch_modes (and gemm.hip's launch_dtype) instantiate
+bool du_gemm_modes_served(int am, int bm) {
+  if (am == DU_PLAIN_ROW) return bm == DU_PLAIN_ROW || bm == DU_PLAIN_COL;
+  if (am == DU_PLAIN_COL) return bm == DU_PLAIN_COL || bm == DU_IM2COL_COL;
+  return am == DU_IM2COL_ROW && bm == DU_PLAIN_ROW;
+}
 
-int du_gemm_nt_p8(const du_gemm_args& a, hipStream_t st, int tail_rows = 0);     // gemm_p8.hip
-bool du_gemm_p8_tail_ok(const du_gemm_args& whole, int r);
-bool du_gemm_p8_wants(const du_gemm_args& a);
-int du_gemm_p8_choice(const du_gemm_args& a);
-bool du_gemm_glds_serves(const du_gemm_args& a);              // gemm_glds.hip
-bool du_gemm_rk_serves(const du_gemm_args& a);                // gemm_rk.hip (short contractions, weights resident in LDS)
-int du_gemm_nt_rk(const du_gemm_args& a, hipStream_t st);
-int du_gemm_tn_p8(const du_gemm_args& a, hipStream_t st);     // gemm_p8.hip (weight gradients)
-int du_gemm_tn_p8_splits(const du_gemm_args& a);
+int du_gemm_bf16_tiles(const du_gemm_args& a, hipStream_t st) {
+  return a.out_dtype == DU_BF16 ? launch_modes<bf16_t>(a, st) : launch_modes<float>(a, st);
+}
+
+bool du_gemm_p8_wants(const du_gemm_args& a);                 // gemm_p8.hip
 
 // Rows of a tall bf16 NT product that should leave the tile grid for the K-parallel skinny kernels (gemm_skinny.hip).
 //  * products served by the 256 x 256 multi-phase kernel (gemm_p8.hip): r = M % 256 when 0 < r <= 64 (the ViT: M = 8 * 1029 =
@@ -502,103 +502,4 @@ int du_gemm_ragged_rows(const du_gemm_args& a) {
   const long full = (long)(a.M / 128) * ((a.N + 127) / 128);
   if (full % slots || full / slots > 2) return 0;
   return r;
-}
-
-long du_gemm_p8_ks_bytes(const du_gemm_args& a);               // gemm_p8.hip
-long du_gemm_p8_tail_bytes(const du_gemm_args& whole);
-long du_gemm_ks_bytes_bf16(const du_gemm_args& a) {
-  if (a.dtype != DU_BF16 || a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW) return 0;
-  du_gemm_args head = a;
-  head.ks_ws = nullptr; head.ks_ws_bytes = 0;      // (the ragged-row rule must not depend on the scratch being asked about)
-  int r = a.M % 256;
-  if (r < 1 || r > 64 || !du_gemm_p8_tail_ok(a, r)) r = 0;
-  head.M = a.M - r;
-  const long pair = du_gemm_p8_ks_bytes(head);
-  // (the sliced units exist in the one-shot tile kernels' launches: choice 1 / 2)
-  const int c = r > 0 ? du_gemm_p8_choice(head) : 0;
-  const long tail = (c == 1 || c == 2) ? du_gemm_p8_tail_bytes(a) : 0;
-  return pair > tail ? pair : tail;
-}
-
-// large contraction-contiguous products: the 256 x 256 multi-phase kernel where it pays, else the 128 x 128 direct-to-LDS kernel
-static int nt_tiles(const du_gemm_args& a, hipStream_t st) {
-  if (du_gemm_p8_wants(a)) {
-    int rc = du_gemm_nt_p8(a, st);
-    if (rc != DU_ERR_UNSUPPORTED) return rc;
-  }
-  return du_gemm_nt_glds(a, st);
-}
-
-// returns DU_ERR_UNSUPPORTED when the generic kernel must be used instead
-int du_gemm_bf16_fast(const du_gemm_args& a, hipStream_t st) {
-  if (a.dtype != DU_BF16) return DU_ERR_UNSUPPORTED;
-  if (a.N % 4 || a.ldc % 4 || (((uintptr_t)a.C) & 15)) return DU_ERR_UNSUPPORTED;
-  if (a.bias && (((uintptr_t)a.bias) & 15)) return DU_ERR_UNSUPPORTED;
-  if (a.gamma && (((uintptr_t)a.gamma) & 15)) return DU_ERR_UNSUPPORTED;
-  if (a.residual && (a.ldr % 4 || (((uintptr_t)a.residual) & 15))) return DU_ERR_UNSUPPORTED;
-  if (a.store_mode == DU_STORE_PIXEL_SHUFFLE2 && a.ps_C % 4) return DU_ERR_UNSUPPORTED;
-  if (a.c_batch_stride % 4) return DU_ERR_UNSUPPORTED;
-  if (a.a_mode == DU_PLAIN_COL && (a.b_mode == DU_PLAIN_COL || a.b_mode == DU_IM2COL_COL)) {     // weight gradients: the multi-phase kernel where it is legal
-    int rc = du_gemm_tn_p8(a, st);
-    if (rc != DU_ERR_UNSUPPORTED) return rc;
-  }
-  if (du_gemm_rk_serves(a)) {        // K <= 256, tall M: the streaming kernel (any M: rows past the last full block are masked)
-    int rc = du_gemm_nt_rk(a, st);
-    if (rc != DU_ERR_UNSUPPORTED) return rc;
-  }
-  {
-    const int r = du_gemm_ragged_rows(a);
-    if (r > 0 && a.ws && a.ws_elems >= du_gemm_skinny_ws_elems(a.N, a.K)) {
-      // exact part on the tile kernel, the short ragged tail on the K-parallel skinny kernels (gemm_skinny.hip)
-      const long m0 = a.M - r;
-      const long osz = a.out_dtype == DU_BF16 ? 2 : 4;
-      du_gemm_args tail = a;
-      tail.M = r;
-      tail.A = (const char*)a.A + m0 * a.lda * 2;
-      tail.C = (char*)a.C + m0 * a.ldc * osz;
-      if (a.residual) tail.residual = (const char*)a.residual + m0 * a.ldr * osz;
-      if (a.row_scale) tail.row_scale = a.row_scale + m0 / a.rs_rows;
-      du_gemm_args head = a;
-      head.M = (int)m0;
-      // round 3: where the head runs on a multi-phase kernel, the tail rides in the SAME launch (extra workgroups behind the tiles)
-      if (du_gemm_p8_wants(head) && du_gemm_p8_tail_ok(a, r)) {
-        const int rc_m = du_gemm_nt_p8(head, st, r);
-        if (rc_m != DU_ERR_UNSUPPORTED) return rc_m;
-      }
-      // (forking the tail onto a side stream with event edges measured slower both times it was tried, inside the hipGraph: round 1 beside
-      // the 128 x 128 kernels 191.6 vs 194.0 slices/s; round 2 beside the multi-phase kernels, 8 KB-LDS tail form, 33.9 vs 33.2 ms per step)
-      int rc = nt_tiles(head, st);
-      if (rc == DU_OK) {
-        rc = du_gemm_skinny(tail, st);
-        if (rc == DU_ERR_UNSUPPORTED) {
-          tail.ws = nullptr; tail.ws_elems = 0;
-          return a.out_dtype == DU_BF16 ? launch_modes<bf16_t>(tail, st) : launch_modes<float>(tail, st);
-        }
-        return rc;
-      }
-      if (rc != DU_ERR_UNSUPPORTED) return rc;
-    }
-    int rc = nt_tiles(a, st);
-    if (rc != DU_ERR_UNSUPPORTED) return rc;
-  }
-  if (a.out_dtype == DU_BF16) return launch_modes<bf16_t>(a, st);
-  return launch_modes<float>(a, st);
-}
-
-// which kernel family du_gemm runs for the bulk of this product (measurement tools name the kernel from this, not from a mirror of the
-// dispatch): 0 generic (gemm.hip), 1 bf16 tile engine (this file), 2 128 x 128 direct-to-LDS (gemm_glds.hip), 3 / 4 the 256 x 256 /
-// 256 x 128 multi-phase kernels (gemm_p8.hip), 5 the multi-phase weight-gradient kernel (gemm_p8.hip, TN form), 6 the persistent 256 x 128
-// kernel (gemm_p8.hip), 7 the resident-weights streaming kernel for K <= 256 (gemm_rk.hip)
-int du_gemm_route_bf16(const du_gemm_args& a) {
-  if (a.dtype != DU_BF16) return 0;
-  if (a.N % 4 || a.ldc % 4 || (((uintptr_t)a.C) & 15)) return 0;
-  if (a.a_mode == DU_PLAIN_COL && du_gemm_tn_p8_splits(a)) return 5;
-  if (du_gemm_rk_serves(a)) return 7;
-  du_gemm_args head = a;
-  const int r = du_gemm_ragged_rows(a);
-  if (r > 0) head.M = a.M - r;
-  const int c = du_gemm_p8_choice(head);
-  if (c == 5) return 8;      // (2 + c = 7 is the resident-weights kernel)
-  if (c) return 2 + c;
-  return du_gemm_glds_serves(head) ? 2 : 1;
 }

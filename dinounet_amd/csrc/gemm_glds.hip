@@ -10,6 +10,7 @@
 // Rows past M / N are clamped (their products are never stored); K must be a multiple of 64.
 #include "common.h"
 #include "gemm_params.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -261,9 +262,8 @@ bool du_gemm_glds_serves(const du_gemm_args& a) {
   return !off;
 }
 
-// returns DU_ERR_UNSUPPORTED when the shape / mode is not served by this kernel (caller falls back to gemm_bf16.hip)
+// du_gemm_plan has checked du_gemm_glds_serves
 int du_gemm_nt_glds(const du_gemm_args& a, hipStream_t st) {
-  if (!du_gemm_glds_serves(a)) return DU_ERR_UNSUPPORTED;
   static const char* var = DU_GETENV("DU_GLDS_VARIANT");             // "3": force the 3-stage BK=32 ring, "2": force the 2-stage BK=64 kernel
   // measured (tools/gemm_bench.py): the 3-stage BK=32 ring wins for short contractions (K <= 512: +8..20 %, more workgroups per
   // CU and a deeper DMA queue), the 2-stage BK=64 kernel for K >= 1024 (fewer barriers per flop)

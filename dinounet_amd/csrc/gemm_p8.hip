@@ -40,6 +40,7 @@
 #include <vector>
 #include "common.h"
 #include "gemm_params.h"
+#include "gemm_plan.h"
 #include "gemm_skinny_body.h"
 
 namespace {
@@ -422,7 +423,7 @@ constexpr int P8_LDS = 256 * P8_STG_LDB * 2;   // 135 168 B >= 2 * BUF_B and >= 
 
 // GA ("gather"): the ConvTranspose2d k2 s2 backward products read their im2col operand in place -- NT: A(m = input pixel, k = (tap, co)) =
 // dy[out pixel (2y + tap/2, 2x + tap%2)][co] (data gradient); TN: B(k = input pixel, n = (tap, co)) likewise (weight gradient).
-// The ragged tail of a tall product inside the tile kernel's own launch (du_gemm_bf16_fast: M = head + r, r <= 64 -- the ViT's 8 x 1029 =
+// The ragged tail of a tall product inside the tile kernel's own launch (du_gemm_plan: M = head + r, r <= 64 -- the ViT's 8 x 1029 =
 // 32 x 256 + 40 rows): workgroups behind the main tiles run the K-parallel skinny program on rows [P.M, P.M + tail_rows).  They are
 // dispatched when the first tiles retire and overlap the stragglers; as launches of their own the 40-row tails cost ~8 us each, 72 of
 // them per dinounet_l step (profiles/r02_launch_counts_v5.txt).
@@ -2454,7 +2455,7 @@ static bool p8_gather_legal(const du_gemm_args& a) {
 }
 
 // true when the multi-phase kernels can run this product at all
-static bool p8_legal(const du_gemm_args& a) {
+bool p8_legal(const du_gemm_args& a) {
   if (a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW || a.dtype != DU_BF16) return false;
   if (a.split_k > 1) return false;
   if (a.store_mode == DU_STORE_MSDA_PREP) {       // offsets | weights product with the sampling-location / softmax epilogue: one tile column
@@ -2584,14 +2585,10 @@ long du_gemm_p8_ks_bytes(const du_gemm_args& a) {
   return ks_shape_ok(a) ? ks_ws_need((long)((a.M + 255) / 256) * ((a.N + 255) / 256)) : 0;
 }
 
-// returns DU_ERR_UNSUPPORTED when these kernels cannot serve the product; the caller then uses gemm_glds.hip
-// tail_rows > 0: rows [a.M, a.M + tail_rows) of the same operands / result are computed in the same launch (p8_tail); the caller has checked
+// c: du_gemm_plan's choice among these kernels (1 .. 5, see du_gemm_p8_choice)
+// tail_rows > 0: rows [a.M, a.M + tail_rows) of the same operands / result are computed in the same launch (p8_tail); the plan has checked
 // du_gemm_p8_tail_ok
-int du_gemm_nt_p8(const du_gemm_args& a, hipStream_t st, int tail_rows) {
-  int c = du_gemm_p8_choice(a);
-  if (c == 0 && a.act == DU_ACT_SWIGLU && p8_legal(a)) c = 2;     // the gate epilogue exists only here: take the narrow tile when the
-                                                                  // heuristic would have preferred another kernel family
-  if (c == 0) return DU_ERR_UNSUPPORTED;
+int du_gemm_nt_p8(const du_gemm_args& a, hipStream_t st, int c, int tail_rows) {
   if (a.a_mode == DU_IM2COL_ROW) return g_p8_sched ? launch_p8<bf16_t, 1, false, true>(a, st) : launch_p8<bf16_t, 0, false, true>(a, st);
   const bool bf = a.out_dtype == DU_BF16;
   const int tr = tail_rows;
@@ -2750,9 +2747,8 @@ extern "C" int du_gemm_tn_group(const du_tn_job* jobs, int njobs, void* stream) 
   return rc;
 }
 
-int du_gemm_tn_p8(const du_gemm_args& a, hipStream_t st) {
-  const int s = du_gemm_tn_p8_splits(a);
-  if (s == 0) return DU_ERR_UNSUPPORTED;
+// s: du_gemm_tn_p8_splits(a), non-zero
+int du_gemm_tn_p8(const du_gemm_args& a, hipStream_t st, int s) {
   if (a.b_mode == DU_IM2COL_COL) return g_p8_sched ? launch_p8_tn<1, true>(a, s, st) : launch_p8_tn<0, true>(a, s, st);
   return g_p8_sched ? launch_p8_tn<1, false>(a, s, st) : launch_p8_tn<0, false>(a, s, st);
 }

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "gemm_params.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -222,8 +223,8 @@ bool du_gemm_rk_serves(const du_gemm_args& a) {
   return true;
 }
 
+// du_gemm_plan has checked du_gemm_rk_serves
 int du_gemm_nt_rk(const du_gemm_args& a, hipStream_t st) {
-  if (!du_gemm_rk_serves(a)) return DU_ERR_UNSUPPORTED;
   RkParams P{};
   P.A = (const bf16_t*)a.A; P.lda = a.lda;
   if (a.a_mode == DU_IM2COL_ROW) { P.gather = 1; P.gWi = a.geom.Wi; P.gHo = a.geom.Ho; P.gWo = a.geom.Wo; P.gC = a.geom.C; }
@@ -259,5 +260,5 @@ int du_gemm_nt_rk(const du_gemm_args& a, hipStream_t st) {
     case 192: return rk_launch<12, 8>(P, st, lds);
     case 256: return rk_launch<16, 8>(P, st, lds);
   }
-  return DU_ERR_UNSUPPORTED;
+  return DU_ERR_BAD_ARG;       // (du_gemm_rk_serves admits these five K only)
 }

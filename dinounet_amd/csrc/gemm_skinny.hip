@@ -13,6 +13,7 @@
 //   (2) gemm_skinny_finish_kernel: sums the slices and applies the du_gemm epilogue (alpha, bias, act, gamma, row_scale, residual).
 // Scratch: du_gemm_ws_elems() floats lent by the caller (du_gemm_args.ws).
 #include "gemm_params.h"
+#include "gemm_plan.h"
 #include "gemm_skinny_body.h"
 
 namespace {
@@ -197,21 +198,28 @@ inline int skinny_slices(int N, int K) {
 // scratch floats for du_gemm_skinny on an (M <= 64) x N x K product
 int64_t du_gemm_skinny_ws_elems(int N, int K) { return (int64_t)skinny_slices(N, K) * 64 * N; }
 
-// C[m][n] = epilogue(sum_k A[m][k] B[n][k]) for M <= 64 rows; plain row-major A, B (k contiguous), plain store.
-// Returns DU_ERR_UNSUPPORTED when the shape is not served (caller falls back to the tile kernels).
-int du_gemm_skinny(const du_gemm_args& a, hipStream_t st) {
-  if (a.dtype != DU_BF16 || a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW || a.store_mode != DU_STORE_PLAIN) return DU_ERR_UNSUPPORTED;
-  if (a.M < 1 || a.M > 64 || a.K % SK_CHUNK || a.N % 4 || a.batch > 1 || a.split_k > 1 || a.lda % 8 || a.ldb % 8) return DU_ERR_UNSUPPORTED;
-  if ((((uintptr_t)a.A) | ((uintptr_t)a.B)) & 15) return DU_ERR_UNSUPPORTED;
-  SkinnyEpi E{};
-  E.C = a.C; E.ldc = a.ldc; E.residual = a.residual; E.ldr = a.ldr; E.bias = a.bias; E.gamma = a.gamma; E.row_scale = a.row_scale;
-  E.alpha = a.alpha; E.act = a.act; E.rs_rows = a.rs_rows > 0 ? a.rs_rows : 1; E.out_bf16 = a.out_dtype == DU_BF16;
+// Which form of du_gemm_skinny serves this product: 0 = none (the tile kernels then), DU_TAIL_SKINNY_FUSED = one launch,
+// DU_TAIL_SKINNY_PAIR = partial + finish through a.ws.
+int du_gemm_skinny_form(const du_gemm_args& a) {
+  if (a.dtype != DU_BF16 || a.a_mode != DU_PLAIN_ROW || a.b_mode != DU_PLAIN_ROW || a.store_mode != DU_STORE_PLAIN) return 0;
+  if (a.M < 1 || a.M > 64 || a.K % SK_CHUNK || a.N % 4 || a.batch > 1 || a.split_k > 1 || a.lda % 8 || a.ldb % 8) return 0;
+  if ((((uintptr_t)a.A) | ((uintptr_t)a.B)) & 15) return 0;
   static const bool no_fuse = DU_GETENV("DU_SKINNY_NO_FUSE") != nullptr;     // A-B aid
   // K > 2048 (fc2 of the ViT, K = 4096): a fragment load touches 32 rows at the SAME column offset, 8 KB apart -- every request of the
   // launch lands on the same few memory channels and the fused form (all workgroups walk K in step) takes 21 us against 14 us for the
-  // split-K pair below, whose slices sit at different column offsets (tools/gemm_ragged.py)
+  // split-K pair, whose slices sit at different column offsets (tools/gemm_ragged.py)
   static const int fuse_kmax = DU_GETENV("DU_SKINNY_FUSE_KMAX") ? atoi(DU_GETENV("DU_SKINNY_FUSE_KMAX")) : 2048;      // A-B aid
-  if (!no_fuse && a.K <= fuse_kmax) {
+  if (!no_fuse && a.K <= fuse_kmax) return DU_TAIL_SKINNY_FUSED;
+  if (!a.ws || a.ws_elems < (int64_t)skinny_slices(a.N, a.K) * 64 * a.N) return 0;
+  return DU_TAIL_SKINNY_PAIR;
+}
+
+// C[m][n] = epilogue(sum_k A[m][k] B[n][k]) for M <= 64 rows; plain row-major A, B (k contiguous), plain store.  `form`: du_gemm_skinny_form's.
+int du_gemm_skinny(const du_gemm_args& a, hipStream_t st, int form) {
+  SkinnyEpi E{};
+  E.C = a.C; E.ldc = a.ldc; E.residual = a.residual; E.ldr = a.ldr; E.bias = a.bias; E.gamma = a.gamma; E.row_scale = a.row_scale;
+  E.alpha = a.alpha; E.act = a.act; E.rs_rows = a.rs_rows > 0 ? a.rs_rows : 1; E.out_bf16 = a.out_dtype == DU_BF16;
+  if (form == DU_TAIL_SKINNY_FUSED) {
     // one launch: every workgroup runs the whole contraction of its 32 columns (4 waves x K/4) and applies the epilogue itself.  The
     // split-K pair below costs two launches + a partial round trip (12 us for 40 rows, 96 times per dinounet_l step)
     // waves per workgroup: enough that a wave walks at most ~4 chunks (K = 1024: 16 waves x 1 chunk, 4096: 16 x 4)
@@ -223,7 +231,6 @@ int du_gemm_skinny(const du_gemm_args& a, hipStream_t st) {
     return launch_skinny_fused<4>(a, E, st);
   }
   const int slices = skinny_slices(a.N, a.K);
-  if (!a.ws || a.ws_elems < (int64_t)slices * 64 * a.N) return DU_ERR_UNSUPPORTED;
   int kps = (a.K + slices - 1) / slices;
   kps = ((kps + SK_CHUNK - 1) / SK_CHUNK) * SK_CHUNK;
   const int used = (a.K + kps - 1) / kps;               // empty trailing slices are dropped

@@ -82,7 +82,8 @@ extern "C" {
                             the caller reduces the slabs in a fixed order (du_splitk_reduce_bf16): bit-reproducible results */
 #define DU_STORE_QKV_HEADS 5 /* as DU_STORE_QKV_ROPE without the rotation and the q scale: the projection (+ bias) stored head-major in the
                                three planes (ps_H / ps_W / ps_C as there), rotated afterwards where it lies by du_qkv_rope_inplace.  Served by the
-                               persistent multi-phase kernel only (M % 256 == 0, K >= 384; DU_ERR_UNSUPPORTED otherwise) */
+                               persistent multi-phase kernel only (K >= 384; M % 256 == 0, or 1 .. 64 rows behind the last full 256-row tile, which ride in
+                               the same launch: du_gemm_plan_describe's tail_rows; DU_ERR_UNSUPPORTED otherwise) */
 #define DU_STORE_MSDA_PREP 6 /* MSDeformAttn's sampling_offsets | attention_weights product (ms_deform_attn.py:188-197) with the reference-point /
                                softmax step in the epilogue: N = heads * 12 columns = [heads x 4 points x (x, y) offsets | heads x 4 logits] (+ bias),
                                fp32; instead of the matrix, C receives the sampling locations (M, heads, 4, 2) = ref[m % ps_C] + offset / (ps_W,
@@ -161,10 +162,21 @@ int64_t du_gemm_ws_elems(const du_gemm_args* args);
 /* Bytes of ks_ws du_gemm would use for `args` (0: nothing in this product meets inside the launch: shape, epilogue, du_set_option keys
    16 / 17). */
 int64_t du_gemm_ks_ws_bytes(const du_gemm_args* args);
-/* Kernel family du_gemm runs for the bulk of `args` (for profilers: names the kernel without mirroring the dispatch): 0 generic,
-   1 bf16 tile engine (gemm_bf16.hip), 2 128 x 128 direct-to-LDS NT kernel (gemm_glds.hip), 3 / 4 the 256 x 256 / 256 x 128
-   multi-phase NT kernels (gemm_p8.hip). */
+/* Kernel family du_gemm runs for the bulk of `args` AS PASSED (ws / ks_ws included: without ws the ragged rows stay in the tile grid and
+   the choice is made for the whole M).  Read from the plan du_gemm executes (csrc/gemm_plan.h), so it is what runs: 0 generic (gemm.hip),
+   1 bf16 tile engine (gemm_bf16.hip), 2 128 x 128 direct-to-LDS NT kernel (gemm_glds.hip), 3 / 4 the 256 x 256 / 256 x 128 multi-phase NT
+   kernels (gemm_p8.hip), 5 the multi-phase weight-gradient kernel (gemm_p8.hip, TN form; also the 4-wave 256 x 128 NT kernel of
+   du_set_option(0, 3)), 6 the persistent 256 x 128 kernel (gemm_p8.hip), 7 the resident-weights streaming kernel for K <= 256
+   (gemm_rk.hip), 8 the 256 x 256 kernel as K-split pairs (gemm_p8.hip, option key 16).  Meaningless where du_gemm refuses `args`. */
 int du_gemm_route(const du_gemm_args* args);
+/* The whole plan du_gemm would execute for `args`, without launching (pure host logic: checkable without a GPU).  Writes 9 values and
+   returns 9 (DU_ERR_BAD_ARG: NULL / n < 9): out[0] what du_gemm would return before any launch (DU_OK, DU_ERR_BAD_ARG, DU_ERR_UNSUPPORTED),
+   [1] family (du_gemm_route), [2] variant: the multi-phase NT kernel 1 .. 5 (256 x 256, 256 x 128, 256 x 128 on 4 waves, persistent,
+   K-split pairs), 0 for the other families, [3] 1 = the ConvTranspose2d k2 s2 operand is gathered from dY in place, [4] tail_rows: rows
+   behind the last full tile row that leave the tile grid, [5] how: 0 none, 1 extra workgroups in the head's launch, 2 the one-launch
+   skinny kernel, 3 the skinny partial + finish pair (through ws), 4 the bf16 tile engine, [6] K splits of family 5, [7] du_gemm_ws_elems,
+   [8] du_gemm_ks_ws_bytes. */
+int du_gemm_plan_describe(const du_gemm_args* args, int64_t* out, int n);
 
 /* ---- grouped weight gradients: several dW = dY^T X products in ONE launch ----------------------------------------------------------
    The reference computes every weight gradient inside its layer's backward (torch autograd: F.linear / conv backward at

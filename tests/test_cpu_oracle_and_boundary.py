@@ -483,7 +483,10 @@ def test_gemm_dispatch_host_logic_without_gpu():
             a.row_scale, a.rs_rows = 0x400000, 5376
         if geom is not None:
             a.geom = geom
-        return int(L.du_gemm_route(C.byref(a))), int(L.du_gemm_ws_elems(C.byref(a)))
+        ws = int(L.du_gemm_ws_elems(C.byref(a)))
+        if ws > 0:                                            # as ops.gemm_raw: the caller lends the scratch the product asks for -- du_gemm_route
+            a.ws, a.ws_elems = 0x500000, ws                   # answers for the arguments as passed, and without it the ragged rows stay in the tile grid
+        return int(L.du_gemm_route(C.byref(a))), ws
 
     # frozen ViT-L, M = 8 * 1029 tokens: 256 x 128 tiles for proj / fc2 (fp32 result + residual: one tile per CU); round 5: the PERSISTENT
     # 256 x 128 kernel (6) for the bf16 products whose narrow tiles come out at >= 2 per CU and cheaper than rounds of wide tiles -- qkv

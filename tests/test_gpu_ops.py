@@ -211,8 +211,12 @@ def test_gemm_k_split_pairs_every_way_through_the_exchange(M, N, K):
     K-split pairs of workgroups (gemm_nt_p8ks_kernel, du_set_option key 16): against the fp32 product; the three ways through the exchange
     (both halves resident; one leaves first and the other finds its flag in the wait loop / at its first look -- forced by the test aids in
     du_set_option key 3) give the SAME bits, repeats are bit-identical, the scratch state is zero again after every launch and the
-    error word (a flag that never came) stays clear; ragged rows ride in the same launch."""
+    error word (a flag that never came) stays clear; ragged rows ride in the same launch (8232 rows).
+    4136 x 1024 x 1024 through ops.mm runs the 128 x 128 kernel (2), as it always did (tests/test_cpu_gemm_plan.py: CORRECTED,
+    'ragged rows without ws', and test_plan_of_the_k_split_pair_shapes_as_ops_lends_scratch): ops.gemm_raw asks for the ragged rows' ws before it lends ks_ws, the pair kernel is not yet legal for
+    the 4096-row head then, no ws is lent, and all 4136 rows (17 x 4 tiles: no whole pairs) stay in one grid."""
     from dinounet_amd import ops, _lib
+    route = 2 if (M, N, K) == (4136, 1024, 1024) else 8
     d = dev()
     bf = torch.bfloat16
     L = _lib.lib()
@@ -227,7 +231,7 @@ def test_gemm_k_split_pairs_every_way_through_the_exchange(M, N, K):
         for aid in (0, 8, 24, 16):
             L.du_set_option(3, aid)
             y = run()
-            assert ops.LAST_GEMM_ROUTE == 8, ops.LAST_GEMM_ROUTE
+            assert ops.LAST_GEMM_ROUTE == route, ops.LAST_GEMM_ROUTE
             for _ in range(10 if aid == 0 else 2):
                 assert torch.equal(run(), y)
             torch.cuda.synchronize()
@@ -2045,3 +2049,74 @@ def test_conv_transpose2x2_on_the_streaming_kernel(B, H, W, Ci, Co):
     assert rel(y, yr) < TOL[bf]
     assert rel(xg.grad, xr.grad) < TOL[bf]
     assert rel(wg.grad, wr.grad) < TOL[bf] and rel(bg.grad, b * 0 + go.float().sum((0, 1, 2))) < TOL[bf]
+
+
+def test_gemm_route_is_what_ran_where_the_old_route_was_wrong():
+    """du_gemm_route is read from the plan du_gemm executes (csrc/gemm_plan.h).  The three kinds of product on which the route used to
+    name another family than the one that ran (tests/test_cpu_gemm_plan.py: CORRECTED), at the smallest shapes that reach them: the
+    result against the fp64 product at this file's bf16 tolerance, and the route / plan.
+      * 256 x 128 x 256 with the bias one float off 16 bytes: the generic kernel (0; aligned: the direct-to-LDS kernel, 2);
+      * SwiGLU at 256 x 256 x 256, two 256 x 128 tiles where the tile heuristic wants 192: the 256 x 128 multi-phase kernel (4), the only
+        family with the gate epilogue (2 was reported);
+      * 1064 x 128 x 256 under du_set_option(0, 2) WITHOUT ws: all 1064 rows on the 256 x 128 kernel (4), no tail kernel; with the
+        scratch ops.gemm_raw lends, 1024 rows and the 40 behind them in the same launch."""
+    import ctypes as C
+    from dinounet_amd import ops, _lib
+    from dinounet_amd._lib import ACT_SWIGLU, DU_BF16, PLAIN_ROW, GemmArgs
+    d = dev()
+    bf = torch.bfloat16
+    L = _lib.lib()
+    plan = (C.c_int64 * 9)()
+
+    def operands(M, N, K):
+        x, w = q(gen(M, K, seed=1), bf).to(d, bf), q(gen(N, K, seed=2, scale=K ** -0.5), bf).to(d, bf)
+        return x, w, x.double() @ w.double().t()
+
+    ops.TRACK_ROUTE = True
+    try:
+        # misaligned bias
+        M, N, K = 256, 128, 256
+        x, w, u = operands(M, N, K)
+        b = gen(N + 1, seed=3).to(d)
+        for off, want in ((0, 2), (1, 0)):
+            out = torch.empty((M, N), dtype=bf, device=d)
+            ops.gemm_raw(dtype=DU_BF16, out_dtype=DU_BF16, a_mode=PLAIN_ROW, b_mode=PLAIN_ROW, M=M, N=N, K=K, A=x.data_ptr(), lda=K, B=w.data_ptr(),
+                         ldb=K, Cmat=out.data_ptr(), ldc=N, bias=b[off:].data_ptr())
+            assert ops.LAST_GEMM_ROUTE == want, (off, ops.LAST_GEMM_ROUTE)
+            assert rel(out, u + b[off:off + N].double()) < TOL[bf]
+        # SwiGLU below the tile heuristic's threshold
+        M, N, K = 256, 256, 256
+        x, w, u = operands(M, N, K)
+        b = gen(N, seed=3).to(d)
+        u = u + b.double()
+        out = torch.empty((M, N // 2), dtype=bf, device=d)
+        ops.gemm_raw(dtype=DU_BF16, out_dtype=DU_BF16, a_mode=PLAIN_ROW, b_mode=PLAIN_ROW, M=M, N=N, K=K, A=x.data_ptr(), lda=K, B=w.data_ptr(),
+                     ldb=K, Cmat=out.data_ptr(), ldc=N // 2, bias=b.data_ptr(), act=ACT_SWIGLU)
+        assert ops.LAST_GEMM_ROUTE == 4, ops.LAST_GEMM_ROUTE
+        assert rel(out, F.silu(u[:, 0::2]) * u[:, 1::2]) < TOL[bf]
+        # ragged rows with and without the scratch
+        M, N, K = 1064, 128, 256
+        x, w, u = operands(M, N, K)
+        L.du_set_option(0, 2)
+        a = GemmArgs()
+        a.dtype = a.out_dtype = DU_BF16
+        a.a_mode = a.b_mode = PLAIN_ROW
+        a.M, a.N, a.K, a.lda, a.ldb, a.ldc, a.batch, a.split_k, a.alpha = M, N, K, K, K, N, 1, 1, 1.0
+        out = torch.empty((M, N), dtype=bf, device=d)
+        a.A, a.B, a.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
+        assert L.du_gemm_plan_describe(C.byref(a), plan, 9) == 9
+        assert list(plan)[:7] == [0, 4, 2, 0, 0, 0, 0] and plan[7] > 0, list(plan)      # the whole M on 256 x 128 tiles, no tail; ws wanted
+        assert L.du_gemm_route(C.byref(a)) == 4
+        _lib.check(L.du_gemm(C.byref(a), ops._st()), "du_gemm")
+        assert rel(out, u) < TOL[bf]
+        ws = torch.empty(int(plan[7]), dtype=torch.float32, device=d)
+        a.ws, a.ws_elems = ws.data_ptr(), ws.numel()
+        assert L.du_gemm_plan_describe(C.byref(a), plan, 9) == 9
+        assert list(plan)[:7] == [0, 4, 2, 0, 40, 1, 0], list(plan)                      # 1024 rows of tiles, 40 riding in the same launch
+        out2 = torch.empty((M, N), dtype=bf, device=d)
+        a.C = out2.data_ptr()
+        _lib.check(L.du_gemm(C.byref(a), ops._st()), "du_gemm")
+        assert rel(out2, u) < TOL[bf]
+    finally:
+        L.du_set_option(0, -1)
+        ops.TRACK_ROUTE = False
