@@ -1180,12 +1180,19 @@ extern "C" int du_msda_prep_bwd(int dtype, const float* attn, const float* gloc,
   return du_check_launch();
 }
 
+// one thread per 16-byte vector up to 8 workgroups per CU (one round of waves), grid-stride beyond: 43 008 workgroups of one vector per
+// thread took 21 rounds on the token pyramid
+static inline int act_bwd_grid(long n, int v) {
+  const long g = (n / v + 255) / 256;
+  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+}
+
 extern "C" int du_act_bwd(int dtype, const void* z, const void* dy, void* dz, int64_t n, int act, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!z || !dy || !dz || n <= 0) return DU_ERR_BAD_ARG;
   DISPATCH_T(dtype,
-             hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3(grid_1d(n)), dim3(256), 0, st, (const bf16_t*)z, (const bf16_t*)dy, (bf16_t*)dz, (long)n, act),
-             hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(grid_1d(n)), dim3(256), 0, st, (const float*)z, (const float*)dy, (float*)dz, (long)n, act));
+             hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3(act_bwd_grid(n, 8)), dim3(256), 0, st, (const bf16_t*)z, (const bf16_t*)dy, (bf16_t*)dz, (long)n, act),
+             hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(act_bwd_grid(n, 4)), dim3(256), 0, st, (const float*)z, (const float*)dy, (float*)dz, (long)n, act));
   return du_check_launch();
 }
 

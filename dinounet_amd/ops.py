@@ -2031,6 +2031,10 @@ class _DWConvSegs(torch.autograd.Function):
         es = x.element_size()
         L = _lib.lib()
         for (off, B, h, ww, ld, bs) in segs:
+            if act == ACT_NONE and L.du_dwconv_band_ok(_code(x.dtype), B, h, ww, Cc, 0):      # band kernels (csrc/dwconv.hip)
+                _lib.check(L.du_dwconv_band_fwd(_code(x.dtype), C.c_void_p(x.data_ptr() + off * es), _p(wf), _p(bf),
+                                                C.c_void_p(y.data_ptr() + off * es), ld, bs, B, h, ww, Cc, _st()), "du_dwconv_band_fwd")
+                continue
             _lib.check(L.du_dwconv3x3_fwd(_code(x.dtype), C.c_void_p(x.data_ptr() + off * es), ld, bs, _p(wf), _p(bf),
                                           C.c_void_p(y.data_ptr() + off * es), ld, bs,
                                           None if z is None else C.c_void_p(z.data_ptr() + off * es), B, h, ww, Cc, act, _st()),
@@ -2056,6 +2060,13 @@ class _DWConvSegs(torch.autograd.Function):
         dw = torch.empty((Cc, 9), dtype=torch.float32, device=x.device)      # written by the first segment, accumulated by the rest
         db = torch.empty(Cc, dtype=torch.float32, device=x.device) if has_bias else None
         for si, (off, B, h, ww, ld, bs) in enumerate(segs):
+            if act == ACT_NONE and L.du_dwconv_band_ok(code, B, h, ww, Cc, 0):
+                n = int(L.du_dwconv_band_ws_elems(code, B, h, ww, Cc, 0))
+                ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
+                _lib.check(L.du_dwconv_band_bwd(code, C.c_void_p(dz.data_ptr() + off * es), C.c_void_p(x.data_ptr() + off * es), _p(wf),
+                                                C.c_void_p(dx.data_ptr() + off * es), _p(dw), _p(db), ld, bs, B, h, ww, Cc, _p(ws), n,
+                                                1 if si > 0 else 0, _st()), "du_dwconv_band_bwd")
+                continue
             _lib.check(L.du_dwconv3x3_bwd_data(code, C.c_void_p(dz.data_ptr() + off * es), ld, bs, _p(wf),
                                                C.c_void_p(dx.data_ptr() + off * es), ld, bs, B, h, ww, Cc, _st()),
                        "du_dwconv3x3_bwd_data")
@@ -2085,8 +2096,13 @@ class _DWConvTokens(torch.autograd.Function):
         wf = _f32(w).view(Cc, 9)
         y = torch.empty_like(x)
         z = torch.empty_like(x) if act != ACT_NONE else None
-        _lib.check(_lib.lib().du_dwconv3x3_tokens_fwd(_code(x.dtype), _p(x), _p(wf), _p(_f32(bias)), _p(y), _p(z), B, H, W, Cc, act, _st()),
-                   "du_dwconv3x3_tokens_fwd")
+        L = _lib.lib()
+        if L.du_dwconv_band_ok(_code(x.dtype), B, H, W, Cc, 1):      # band kernels (csrc/dwconv.hip)
+            _lib.check(L.du_dwconv_band_tokens_fwd(_code(x.dtype), _p(x), _p(wf), _p(_f32(bias)), _p(y), _p(z), B, H, W, Cc, act, _st()),
+                       "du_dwconv_band_tokens_fwd")
+        else:
+            _lib.check(L.du_dwconv3x3_tokens_fwd(_code(x.dtype), _p(x), _p(wf), _p(_f32(bias)), _p(y), _p(z), B, H, W, Cc, act, _st()),
+                       "du_dwconv3x3_tokens_fwd")
         ctx.save_for_backward(x, wf, z)
         ctx.conf = (H, W, act, bias is not None)
         return y
@@ -2099,6 +2115,17 @@ class _DWConvTokens(torch.autograd.Function):
         L = _lib.lib()
         code = _code(x.dtype)
         dy = dy.contiguous()
+        if L.du_dwconv_band_ok(code, B, H, W, Cc, 1):
+            # the data gradient applies act' on load and leaves dz for the weight gradient: no du_act_bwd pass
+            dz = torch.empty_like(dy) if act != ACT_NONE else None
+            dx = torch.empty_like(x)
+            dw = torch.empty((Cc, 9), dtype=torch.float32, device=x.device)
+            db = torch.empty(Cc, dtype=torch.float32, device=x.device) if has_bias else None
+            n = int(L.du_dwconv_band_ws_elems(code, B, H, W, Cc, 1))
+            ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
+            _lib.check(L.du_dwconv_band_tokens_bwd(code, _p(z), _p(dy), _p(x), _p(wf), _p(dx), _p(dw), _p(db), _p(dz), B, H, W, Cc, act,
+                                                   _p(ws), n, _st()), "du_dwconv_band_tokens_bwd")
+            return dx, dw.view(Cc, 1, 3, 3), db, None, None, None
         if act != ACT_NONE:
             dz = torch.empty_like(dy)
             _lib.check(L.du_act_bwd(code, _p(z), _p(dy), _p(dz), dy.numel(), act, _st()), "du_act_bwd")

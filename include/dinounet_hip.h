@@ -23,8 +23,9 @@
  *   du_layernorm_fwd / _bwd      <- nn.LayerNorm (layers/block.py:43,56; dinov3_adapter.py:128-137)
  *   du_chan_stats / du_norm_act_* <- InstanceNorm2d+LeakyReLU (dinounet_training.py:401,238; decoder
  *          StackedConvBlocks :581-592) and SyncBatchNorm(+ReLU) (dinov3_adapter.py:242-270,361-364)
- *   du_dwconv3x3_*               <- DWConv (dinov3_adapter.py:94-109), DepthwiseSeparableConv.depthwise
- *          (dinounet_training.py:235)
+ *   du_dwconv3x3_* / du_dwconv_band_* <- DWConv (dinov3_adapter.py:94-109), DepthwiseSeparableConv.depthwise
+ *          (dinounet_training.py:235): du_dwconv_band_* (dwconv.hip: a workgroup walks a band of rows, GELU backward
+ *          fused into the data gradient) where du_dwconv_band_ok, du_dwconv3x3_* (elementwise.hip) for every other shape
  *   du_maxpool3x3s2_*            <- nn.MaxPool2d(3,2,1) (dinov3_adapter.py:250)
  *   du_bilinear_add_*            <- F.interpolate(bilinear, align_corners=False)+add (dinov3_adapter.py:472-476)
  *   du_se_gate_* / du_se_scale_*  <- SqueezeExcitation + residual (dinounet_training.py:210-225,438)
@@ -381,6 +382,24 @@ int du_dwconv3x3_tokens_fwd(int dtype, const void* x, const float* w, const floa
 int du_dwconv3x3_tokens_bwd_data(int dtype, const void* dy, const float* w, void* dx, int B, int H, int W, int C, void* stream);
 int du_dwconv3x3_tokens_bwd_weight(int dtype, const void* x, const void* dy, float* dw, float* db, int B, int H, int W, int C, float* ws,
                                    int64_t ws_elems, void* stream);
+/* Band-tiled forms of the kernels above (csrc/dwconv.hip): bf16, C % 8 == 0, every grid width even.  du_dwconv_band_ok returns 1 exactly
+   when they will run for (B, H, W, C) -- pyramid != 0: the token pyramid of du_dwconv3x3_tokens_* (H, W as there), else one NHWC segment --
+   and 0 otherwise (fp32, odd widths, C % 8, du_set_option(19, 0)): the caller then uses du_dwconv3x3_*.  y, z and dx have the bits of the
+   kernels above; dw / db are the same fp32 sums in another order.
+   _tokens_bwd: z (pre-activation) and dz (scratch, same shape as dy) are needed when act != DU_ACT_NONE and may be NULL otherwise: the
+   data gradient forms dz = bf16(dy * act'(z)) on load (no du_act_bwd pass), writes dx and leaves dz for the weight gradient.  It OVERWRITES
+   dx, dw (C,9) and db (C, nullable).  _bwd (one NHWC segment, no activation; x, dy, dx share ld / bs): accumulate = 1 adds to dw / db.
+   ws: du_dwconv_band_ws_elems floats (one partial row per workgroup, summed by one small second launch). */
+int du_dwconv_band_ok(int dtype, int B, int H, int W, int C, int pyramid);
+int64_t du_dwconv_band_ws_elems(int dtype, int B, int H, int W, int C, int pyramid);
+int du_dwconv_band_tokens_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, void* z, int B, int H, int W, int C,
+                              int act, void* stream);
+int du_dwconv_band_tokens_bwd(int dtype, const void* z, const void* dy, const void* x, const float* w, void* dx, float* dw, float* db,
+                              void* dz, int B, int H, int W, int C, int act, float* ws, int64_t ws_elems, void* stream);
+int du_dwconv_band_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, int64_t ld, int64_t bs, int B, int H, int W,
+                       int C, void* stream);
+int du_dwconv_band_bwd(int dtype, const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, int64_t ld, int64_t bs,
+                       int B, int H, int W, int C, float* ws, int64_t ws_elems, int accumulate, void* stream);
 /* MaxPool2d(3, 2, 1) on contiguous NHWC; idx (nullable, same shape as y, uint8) records the winning tap */
 int du_maxpool3x3s2_fwd(int dtype, const void* x, void* y, uint8_t* idx, int B, int H, int W, int C, void* stream);
 int du_maxpool3x3s2_bwd(int dtype, const uint8_t* idx, const void* dy, void* dx, int B, int H, int W, int C, void* stream);
@@ -558,6 +577,9 @@ int du_device_ok(void); /* 1 if the current device is gfx950 */
            meet through du_gemm_args.ks_ws: 1 (default), 0 = one unit per 32 columns walks the whole contraction;
    key 18: du_layernorm_fwd with two rows per wave: 1 = where the rows overflow one round of waves (32 per CU) by less than 2x -- the ViT's
            8232 rows (default), 0 = never, 2 = always;
+   key 19: depthwise 3 x 3 on the band kernels (dwconv.hip) where du_dwconv_band_ok: 1 (default), 0 = the kernels of elementwise.hip
+           everywhere (du_dwconv_band_ok then returns 0); tuning aid: bits 0-7 >= 2 = bands of that many rows in forward and data
+           gradient, bits 8-15 >= 2 = in the weight gradient, instead of the height the library picks;
    key 14: bf16 products with a bf16 residual on the persistent kernel (the residual as two more K-steps): 1 (default), 0 = one-shot kernels;
    key 9: number of independent products the caller keeps in flight on DIFFERENT streams (default 1; dinounet_amd runs the frozen ViT as
           two half-batch chains): du_gemm's tile choice then counts workgroup rounds on 256 / value CUs. */
