@@ -664,6 +664,28 @@ int du_surface_field(const uint16_t* bits, double* field, int D, int H, int W, i
 int du_surface_gather(const uint16_t* bits, int D, int H, int W, int R, int active, double sz, double sy, double sx,
                       const int64_t* seg_off_host, double* dist_sq, double* sqrt_sums, void* ws, int64_t ws_elems, void* stream);
 
+/* ---- connected components of one mask of a label map, and "keep only the largest" (csrc/cc.hip;
+   remove_all_but_largest_component_from_segmentation, dinounet/postprocessing/remove_connected_components.py:22-34).  seg (D, H, W) uint8,
+   read-only; a voxel is in the mask if its label is < 64 and bit `label` of mask_bits is set (the du_labels_to_regions convention: the OR of
+   the masks of a list of labels / regions; any other label is in no mask).  Full connectivity: 26 neighbours (8 in-plane with D == 1, fewer
+   along any axis of extent 1).  The id of a component is the smallest linear index (z H + y) W + x of its voxels, so the labelling depends
+   on the input alone; the largest component has the most voxels, on a tie the smallest id (the first in raster order).
+   du_cc_label: ids (D, H, W) int32 = the id of the voxel's component, -1 outside the mask; stats (3) int64 DEVICE = {n_components, size of
+   the largest, id of the largest or -1 without one}.
+   du_cc_keep_largest: out (D, H, W) uint8, every voxel written = background_label (0..255) where the voxel is in the mask but not in the
+   largest component, else seg; an empty mask copies seg.  out must not overlap seg (DU_ERR_BAD_ARG).  stats as above.
+   ws: du_cc_ws_elems(D, H, W, keep) int32 elements, 16-byte aligned, keep = 0 for du_cc_label, 1 for du_cc_keep_largest
+   = 4 + (2 + keep) * n4, n4 = D H W rounded up to a multiple of 4: parent and size fields (8 bytes per voxel), for keep_largest the
+   ids too (12 bytes per voxel).  Five kernels and one 16-byte memset on `stream` (six kernels for keep_largest), none waits for another workgroup; integer atomics
+   only, so results are bit-identical from run to run.
+   DU_ERR_UNSUPPORTED: D H W >= 2^31.  DU_ERR_BAD_ARG: a NULL pointer, an extent < 1, ws misaligned or ws_elems below du_cc_ws_elems (which
+   is 0 for a shape with an error). ---- */
+int64_t du_cc_ws_elems(int D, int H, int W, int keep);
+int du_cc_label(const uint8_t* seg, int64_t mask_bits, int32_t* ids, int64_t* stats, int D, int H, int W, int32_t* ws, int64_t ws_elems,
+                void* stream);
+int du_cc_keep_largest(const uint8_t* seg, int64_t mask_bits, int background_label, uint8_t* out, int64_t* stats, int D, int H, int W,
+                       int32_t* ws, int64_t ws_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
