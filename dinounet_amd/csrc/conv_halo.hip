@@ -13,7 +13,7 @@
 //
 // Roofline: HBM for Cout <= 64 at 256^2 / 512^2 (algorithmic bytes = (Cin + Cout) * 2 per pixel), MFMA for the 128-channel layers.
 #include <stdlib.h>
-#include "common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -290,17 +290,18 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(HaloParams P) {
   }
 }
 
-template <int CK, int TN>
-int launch(const HaloParams& P, hipStream_t st) {
-  constexpr int COUT = TN * 32, LD = CK + 8;
-  constexpr int HROW = ((HXW * LD * 2 + 255) / 256 * 256) / 2;
-  const int nch = P.Cin / CK;
+// dynamic LDS of conv3x3_halo_kernel<CK, TN>: the weights stay resident behind the halo when Cin is one chunk, else the fp32 tile lies over them
+constexpr size_t halo_lds(int CK, int TN, bool one_chunk) {
+  const int COUT = TN * 32, LD = CK + 8;
+  const int HROW = ((HXW * LD * 2 + 255) / 256 * 256) / 2;
   const size_t main_bytes = (size_t)(9 * COUT * LD + (TH + 2) * HROW) * 2;
   const size_t stg_bytes = (size_t)128 * (COUT + 4) * 4 + (size_t)4 * COUT * 2 * 4;   // fp32 tile + statistics scratch [4][COUT][2]
-  const size_t lds = (nch == 1 ? main_bytes + stg_bytes : (main_bytes > stg_bytes ? main_bytes : stg_bytes)) + (size_t)COUT * 4;   // + bias
-  if (lds > 160 * 1024) return DU_ERR_UNSUPPORTED;
-  // the halo loads address one image through a 32-bit buffer descriptor whose out-of-range sentinel is offset 2^31
-  if ((long)P.H * P.W * (P.ldx > P.ldx2 ? P.ldx : P.ldx2) * 2 >= (1L << 31)) return DU_ERR_UNSUPPORTED;
+  return (one_chunk ? main_bytes + stg_bytes : (main_bytes > stg_bytes ? main_bytes : stg_bytes)) + (size_t)COUT * 4;   // + bias
+}
+
+template <int CK, int TN>
+int launch(const HaloParams& P, hipStream_t st) {
+  const size_t lds = halo_lds(CK, TN, P.Cin == CK);
   auto kfn = conv3x3_halo_kernel<CK, TN>;
   if (hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DU_ERR_LAUNCH;
   const int per_cu = (int)((160 * 1024) / lds);
@@ -312,37 +313,73 @@ int launch(const HaloParams& P, hipStream_t st) {
 
 }  // namespace
 
-// x (B,H,W,C1) [+ x2 (B,H,W,Cin-C1)] NHWC bf16 with pixel strides ldx/ldx2; w bf16 [Cout][9*Cin] in (tap, ci) column order;
-// y (B,H,W,Cout) bf16, pixel stride ldy.  stats_part (nullable): (du_conv3x3_halo_parts(...), Cout, 2) fp32 partial sums, image-major.
-// Returns DU_ERR_UNSUPPORTED for shapes this kernel does not serve (caller falls back to the implicit-GEMM path).
-extern "C" int du_conv3x3_halo(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
-                               const void* w, const float* bias, void* y, int64_t ldy, float* stats_part, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return DU_ERR_BAD_ARG;
-  if (H % TH || W % TW || ldx % 8 || ldy % 8 || (x2 && (ldx2 % 8 || C1 % 8)) || Cin % 8) return DU_ERR_UNSUPPORTED;
-  if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)x2)) & 15) return DU_ERR_UNSUPPORTED;
-  if (!x2) C1 = Cin;
-  {                // streaming strip kernel (conv_strip.hip) where it serves the shape
-    const int rc = du_conv3x3_strip(x, ldx, x2, ldx2, C1, Cin, Cout, B, H, W, w, bias, y, ldy, stats_part, stream);
-    if (rc != DU_ERR_UNSUPPORTED) return rc;
-    // The caller sized stats_part with du_conv3x3_halo_parts(), which knows the channel counts and the image but not the strides / byte
-    // sizes the strip kernel also declines on (a per-image input >= 1 GiB, an output >= 2 GiB).  When the strip kernel was the planned
-    // one, the tile kernel below would write B * (H / 8) * (W / 16) partial rows into a buffer of B * (H / rs) * (W / 32) and the
-    // finalize step would run with the wrong count: decline instead (the caller retries without epilogue statistics).
-    if (stats_part && du_conv3x3_halo_parts(C1, Cin, Cout, B, H, W) != B * (H / TH) * (W / TW)) return DU_ERR_UNSUPPORTED;
+Conv3x3Plan du_conv3x3_plan(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
+                            const void* w, const void* y, int64_t ldy, bool want_stats) {
+  Conv3x3Plan p{DU_ERR_UNSUPPORTED, DU_CONV_NONE, 0, 0, 0};
+  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) { p.rc = DU_ERR_BAD_ARG; return p; }
+  if (H % TH || W % TW || ldx % 8 || ldy % 8 || (x2 && (ldx2 % 8 || C1 % 8)) || Cin % 8) return p;
+  if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)x2)) & 15) return p;
+  if (!x2) { C1 = Cin; ldx2 = 0; }
+  const int64_t ldmax = ldx > ldx2 ? ldx : ldx2;
+  // streaming strip kernel (conv_strip.hip) where it serves the shape and reaches the tensors
+  const int strip = du_conv3x3_strip_kind(C1, Cin, Cout, x2 != nullptr, B, H, W, &p.strip_rows);
+  if (strip && du_conv3x3_strip_fits(B, H, W, ldmax, ldy)) {
+    p.rc = DU_OK; p.kernel = DU_CONV_STRIP; p.variant = strip;
+    p.stats_parts = want_stats ? B * (H / p.strip_rows) * (W / 32) : 0;
+    return p;
   }
-  HaloParams P{};
-  P.x = (const bf16_t*)x; P.ldx = ldx; P.x2 = (const bf16_t*)x2; P.ldx2 = ldx2; P.C1 = C1; P.Cin = Cin; P.Cout = Cout;
-  P.B = B; P.H = H; P.W = W; P.w = (const bf16_t*)w; P.bias = bias; P.y = (bf16_t*)y; P.ldy = ldy; P.stats_part = stats_part;
-  P.tilesX = W / TW; P.tilesY = H / TH; P.ntiles = B * P.tilesX * P.tilesY;
-  // channel chunk: 64 when both sources split on 64-channel boundaries, else 32
+  // LDS-tiled kernel.  Channel chunk: 64 when both sources split on 64-channel boundaries, else 32
   static const bool ck32 = DU_GETENV("DU_HALO_CK32") != nullptr;     // A-B aid: 32-channel chunks for the 64-output layers too (2 workgroups / CU)
   const bool c64 = Cin % 64 == 0 && C1 % 64 == 0;
   const bool c32 = Cin % 32 == 0 && C1 % 32 == 0;
-  if (Cout == 32) { if (c64) return launch<64, 1>(P, st); if (c32) return launch<32, 1>(P, st); }
-  if (Cout == 64) { if (c64 && !ck32) return launch<64, 2>(P, st); if (c32) return launch<32, 2>(P, st); }
-  if (Cout == 128) { if (c32) return launch<32, 4>(P, st); }
+  const int ck = c64 && !(ck32 && Cout == 64) && Cout != 128 ? 64 : 32;
+  if (!c32 || !(Cout == 32 || Cout == 64 || Cout == 128)) return p;
+  if (halo_lds(ck, Cout / 32, Cin == ck) > 160 * 1024) return p;     // (32 -> 128 channels: weights, halo and the fp32 tile side by side)
+  // the halo loads address one image through a 32-bit buffer descriptor whose out-of-range sentinel is offset 2^31
+  if ((long)H * W * ldmax * 2 >= (1L << 31)) return p;
+  p.rc = DU_OK; p.kernel = DU_CONV_HALO; p.variant = ck * 10 + Cout / 32;
+  // a strip shape the strip kernel declined on its byte sizes runs here without statistics (its callers size their buffers for strips)
+  p.stats_parts = want_stats && !strip ? B * (H / TH) * (W / TW) : 0;
+  return p;
+}
+
+// x (B,H,W,C1) [+ x2 (B,H,W,Cin-C1)] NHWC bf16 with pixel strides ldx/ldx2; w bf16 [Cout][9*Cin] in (tap, ci) column order;
+// y (B,H,W,Cout) bf16, pixel stride ldy.  stats_part (nullable): (plan's stats_parts, Cout, 2) fp32 partial sums, image-major.
+// Executes du_conv3x3_plan: DU_ERR_UNSUPPORTED for calls no kernel serves (caller falls back to the implicit-GEMM path), and for a
+// stats_part where the plan serves no statistics.
+extern "C" int du_conv3x3_halo(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
+                               const void* w, const float* bias, void* y, int64_t ldy, float* stats_part, void* stream) {
+  const Conv3x3Plan p = du_conv3x3_plan(x, ldx, x2, ldx2, C1, Cin, Cout, B, H, W, w, y, ldy, stats_part != nullptr);
+  if (p.rc != DU_OK) return p.rc;
+  if (stats_part && !p.stats_parts) return DU_ERR_UNSUPPORTED;
+  if (p.kernel == DU_CONV_STRIP) return du_conv3x3_strip_run(p, x, ldx, x2, ldx2, Cout, B, H, W, w, bias, y, ldy, stats_part, stream);
+  hipStream_t st = (hipStream_t)stream;
+  HaloParams P{};
+  P.x = (const bf16_t*)x; P.ldx = ldx; P.x2 = (const bf16_t*)x2; P.ldx2 = ldx2; P.C1 = x2 ? C1 : Cin; P.Cin = Cin; P.Cout = Cout;
+  P.B = B; P.H = H; P.W = W; P.w = (const bf16_t*)w; P.bias = bias; P.y = (bf16_t*)y; P.ldy = ldy; P.stats_part = stats_part;
+  P.tilesX = W / TW; P.tilesY = H / TH; P.ntiles = B * P.tilesX * P.tilesY;
+  switch (p.variant) {
+    case 641: return launch<64, 1>(P, st);
+    case 321: return launch<32, 1>(P, st);
+    case 642: return launch<64, 2>(P, st);
+    case 322: return launch<32, 2>(P, st);
+    case 324: return launch<32, 4>(P, st);
+  }
   return DU_ERR_UNSUPPORTED;
+}
+
+// the plan of a dense, 16-byte aligned call (pixel strides = channel counts; a second source exactly when C1 != Cin) with statistics: its rows
+extern "C" int du_conv3x3_halo_parts(int C1, int Cin, int Cout, int B, int H, int W) {
+  const void* const a = (const void*)16;
+  return du_conv3x3_plan(a, C1, C1 != Cin ? a : nullptr, Cin - C1, C1, Cin, Cout, B, H, W, a, a, Cout, true).stats_parts;
+}
+
+extern "C" int du_conv3x3_plan_describe(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H,
+                                        int W, const void* w, const void* y, int64_t ldy, int want_stats, int64_t* out, int n) {
+  if (!out || n < 4) return DU_ERR_BAD_ARG;
+  const Conv3x3Plan p = du_conv3x3_plan(x, ldx, x2, ldx2, C1, Cin, Cout, B, H, W, w, y, ldy, want_stats != 0);
+  out[0] = p.rc; out[1] = p.kernel; out[2] = p.variant; out[3] = p.stats_parts;
+  return 4;
 }
 
 // =====================================================================================================================
@@ -806,63 +843,88 @@ int g_wgrad_rows = 1;     // du_set_option key 13: 1 = conv3x3_wgrad_rows_kernel
                           // (default); 2 = 128 output channels on the rows kernel too (round 6: 106 / 200 us for the two layers against 400 us of
                           // grouped launch, but x1.0001 in the step -- profiles/r06_ab_wgrad128_side_v1.txt -- so it stays opt-in); 0 = the round-3 kernel
 
-// number of workgroups (= partial dW slabs) the weight-gradient kernel uses for this shape; 0 = shape not served
-extern "C" int du_conv3x3_wgrad_halo_blocks(int C1, int Cin, int Cout, int B, int H, int W) {
-  if (H % TH || W % TW || B <= 0) return 0;
+Conv3x3WgradPlan du_conv3x3_wgrad_plan(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H,
+                                       int W, const void* dy, int64_t lddy) {
+  Conv3x3WgradPlan p{DU_ERR_UNSUPPORTED, DU_WGRAD_NONE, 0, 0};
+  if (!x || !dy) { p.rc = DU_ERR_BAD_ARG; return p; }
+  if (!x2) C1 = Cin;
+  if (H <= 0 || W <= 0 || H % TH || W % TW || B <= 0 || Cin <= 0 || Cin % 32 || C1 % 32 || ldx % 8 || lddy % 8 || (x2 && ldx2 % 8)) return p;
+  if ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)x2)) & 15) return p;
   const int ntiles = B * (H / TH) * (W / TW);
-  if (Cout == 128 && g_wgrad_rows >= 2 && Cin % 32 == 0 && C1 % 32 == 0 && Cin <= 256 &&
-      (long)B * H * W * (Cin > 128 ? Cin : 128) * 2 < 0x7fffffffL) {
+  const bool c64 = Cin % 64 == 0 && C1 % 64 == 0;
+  // the rows kernel addresses the three tensors through 32-bit buffer offsets
+  const long pix = (long)B * H * W, lim = 0x7fffffffL;
+  const bool small = pix * ldx * 2 < lim && pix * lddy * 2 < lim && (!x2 || pix * ldx2 * 2 < lim);
+  int cap;
+  if (Cout == 128) {
     // round 6: the 128-output layers of the first decoder stage (dinounet_training.py:581-592) on the rows kernel, one 32-output block per
-    // wave over 32-channel input chunks; the partial slabs are 0.6-1.2 MB each: 128 workgroups (75-150 MB for the finalize pass to read)
-    return ntiles < 128 ? ntiles : 128;
+    // wave over 32-channel input chunks; the partial slabs are 0.6-1.2 MB each: 128 workgroups (75-150 MB for the finalize pass to read).
+    // (The round-3 kernel's 9 accumulator tiles per wave spill at 128 outputs; the form was admitted for inputs that fit the offsets as
+    // ONE tensor of Cin channels, and stays there.)
+    if (!(g_wgrad_rows >= 2 && small && Cin <= 256 && pix * (Cin > 128 ? Cin : 128) * 2 < lim)) return p;
+    p.kernel = DU_WGRAD_ROWS; p.variant = 324; cap = 128;
+  } else {
+    if (!(Cout == 32 || Cout == 64)) return p;
+    if ((long)Cout * 9 * Cin > 80L * 1024) return p;                 // larger filters: MFMA-bound anyway, partial slabs too big
+    const bool rows = g_wgrad_rows && small;
+    p.kernel = rows ? DU_WGRAD_ROWS : DU_WGRAD_ROUND3;
+    // (round-3 kernel at 64 outputs: 32-channel chunks, 5 accumulator tiles per wave, no spills)
+    p.variant = (c64 && (rows || Cout == 32) ? 640 : 320) + Cout / 32;
+    // persistent workgroups = partial dW slabs.  36-50 KB of LDS and 4 waves each: one per CU leaves every SIMD with a single wave and
+    // nothing to switch to while it waits for its LDS writes / barrier / transpose reads (1.4 TB/s measured); two per CU double the
+    // slab traffic of the finalize (<= 2 x 75 MB) and hide that latency.  DU_HALO_WGRAD_BLOCKS overrides (A-B aid).
+    // measured (bench A-B, round 3): 512^2 64->32 257 -> 168 us, 32->32 138 -> 93 us with 512 workgroups; the 64-output layers at 256^2
+    // (147-295 KB slabs) lose 10 % to the doubled finalize traffic: two per CU only while a slab stays under 80 KB
+    static const int cap_env = DU_GETENV("DU_HALO_WGRAD_BLOCKS") ? atoi(DU_GETENV("DU_HALO_WGRAD_BLOCKS")) : 0;
+    cap = cap_env > 0 ? cap_env : ((long)Cout * 9 * Cin * 4 <= 80L * 1024 ? 512 : 256);
+    // rows kernel: two LDS stages; all forms but 32 -> 32 channels run one workgroup per CU (72-118 KB), so a second slab per CU buys nothing.
+    // Keyed on the kernel named above: past the 32-bit offset limit the round-3 kernel keeps the workgroup count it was tuned for
+    if (rows && cap_env <= 0 && (Cout == 64 || c64)) cap = 256;
   }
-  if (!(Cout == 32 || Cout == 64) || Cin % 32 || C1 % 32) return 0;   // (round-3 kernel: 9 accumulator tiles per wave spill at 128 outputs)
-  if ((long)Cout * 9 * Cin > 80L * 1024) return 0;                 // larger filters: MFMA-bound anyway, partial slabs too big
-  // persistent workgroups = partial dW slabs.  36-50 KB of LDS and 4 waves each: one per CU leaves every SIMD with a single wave and
-  // nothing to switch to while it waits for its LDS writes / barrier / transpose reads (1.4 TB/s measured); two per CU double the
-  // slab traffic of the finalize (<= 2 x 75 MB) and hide that latency.  DU_HALO_WGRAD_BLOCKS overrides (A-B aid).
-  // measured (bench A-B, round 3): 512^2 64->32 257 -> 168 us, 32->32 138 -> 93 us with 512 workgroups; the 64-output layers at 256^2
-  // (147-295 KB slabs) lose 10 % to the doubled finalize traffic: two per CU only while a slab stays under 80 KB
-  static const int cap_env = DU_GETENV("DU_HALO_WGRAD_BLOCKS") ? atoi(DU_GETENV("DU_HALO_WGRAD_BLOCKS")) : 0;
-  int cap = cap_env > 0 ? cap_env : ((long)Cout * 9 * Cin * 4 <= 80L * 1024 ? 512 : 256);
-  // round-5 kernel: two LDS stages; all forms but 32 -> 32 channels run one workgroup per CU (72-118 KB), so a second slab per CU buys nothing
-  // (keyed on the kernel that will run: past the 32-bit offset limit -- judged here on the dense tensors, ld = channels -- the round-3
-  //  kernel takes the shape and keeps the workgroup count it was tuned for)
-  const long pix = (long)B * H * W;
-  const bool small = pix * (Cin > C1 ? Cin : C1) * 2 < 0x7fffffffL && pix * Cout * 2 < 0x7fffffffL;
-  if (g_wgrad_rows && small && cap_env <= 0 && (Cout == 64 || (Cin % 64 == 0 && C1 % 64 == 0))) cap = 256;
-  return ntiles < cap ? ntiles : cap;
+  p.rc = DU_OK; p.blocks = ntiles < cap ? ntiles : cap;
+  return p;
 }
 
-// x / x2 as in du_conv3x3_halo, dy (B,H,W,Cout) bf16; part: du_conv3x3_wgrad_halo_blocks(...) x Cout x 9*Cin fp32 scratch;
-// dw (Cout, 9*Cin) fp32 in (tap, ci) column order is OVERWRITTEN (sum of the partial slabs, via du_strip_finalize).
+// the plan of a dense, 16-byte aligned call (pixel strides = channel counts; a second source exactly when C1 != Cin): its workgroups
+// (= partial dW slabs); 0 = not served
+extern "C" int du_conv3x3_wgrad_halo_blocks(int C1, int Cin, int Cout, int B, int H, int W) {
+  const void* const a = (const void*)16;
+  return du_conv3x3_wgrad_plan(a, C1, C1 != Cin ? a : nullptr, Cin - C1, C1, Cin, Cout, B, H, W, a, Cout).blocks;
+}
+
+extern "C" int du_conv3x3_wgrad_plan_describe(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B,
+                                              int H, int W, const void* dy, int64_t lddy, int64_t* out, int n) {
+  if (!out || n < 4) return DU_ERR_BAD_ARG;
+  const Conv3x3WgradPlan p = du_conv3x3_wgrad_plan(x, ldx, x2, ldx2, C1, Cin, Cout, B, H, W, dy, lddy);
+  out[0] = p.rc; out[1] = p.kernel; out[2] = p.variant; out[3] = p.blocks;
+  return 4;
+}
+
+// x / x2 as in du_conv3x3_halo, dy (B,H,W,Cout) bf16; part: (plan's blocks) x Cout x 9*Cin fp32 scratch; dw (Cout, 9*Cin) fp32 in
+// (tap, ci) column order is OVERWRITTEN (sum of the partial slabs, via du_strip_finalize).  Executes du_conv3x3_wgrad_plan.
 extern "C" int du_conv3x3_wgrad_halo(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H,
                                      int W, const void* dy, int64_t lddy, float* part, float* dw, int with_db, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (!x || !dy || !part || !dw) return DU_ERR_BAD_ARG;
-  if (!x2) C1 = Cin;
-  const int blocks = du_conv3x3_wgrad_halo_blocks(C1, Cin, Cout, B, H, W);
-  if (blocks <= 0 || ldx % 8 || lddy % 8 || (x2 && ldx2 % 8)) return DU_ERR_UNSUPPORTED;
-  if ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)x2)) & 15) return DU_ERR_UNSUPPORTED;
+  if (!part || !dw) return DU_ERR_BAD_ARG;
+  const Conv3x3WgradPlan p = du_conv3x3_wgrad_plan(x, ldx, x2, ldx2, C1, Cin, Cout, B, H, W, dy, lddy);
+  if (p.rc != DU_OK) return p.rc;
   WgradParams P{};
-  P.x = (const bf16_t*)x; P.ldx = ldx; P.x2 = (const bf16_t*)x2; P.ldx2 = ldx2; P.C1 = C1; P.Cin = Cin; P.Cout = Cout;
+  P.x = (const bf16_t*)x; P.ldx = ldx; P.x2 = (const bf16_t*)x2; P.ldx2 = ldx2; P.C1 = x2 ? C1 : Cin; P.Cin = Cin; P.Cout = Cout;
   P.dy = (const bf16_t*)dy; P.lddy = lddy; P.B = B; P.H = H; P.W = W; P.part = part;
   P.tilesX = W / TW; P.tilesY = H / TH; P.ntiles = B * P.tilesX * P.tilesY;
   P.with_db = with_db ? 1 : 0;
-  const bool c64 = Cin % 64 == 0 && C1 % 64 == 0;
   int rc = DU_ERR_UNSUPPORTED;
-  // the round-5 kernel addresses the three tensors through 32-bit buffer offsets
-  const long pix = (long)B * H * W;
-  const bool small = pix * ldx * 2 < 0x7fffffffL && pix * lddy * 2 < 0x7fffffffL && (!x2 || pix * ldx2 * 2 < 0x7fffffffL);
-  if (Cout == 128) {
-    if (!(g_wgrad_rows >= 2 && small)) return DU_ERR_UNSUPPORTED;
-    rc = launch_wgrad_rows<32, 4>(P, blocks, st);
-  } else if (g_wgrad_rows && small) {
-    if (Cout == 32) rc = c64 ? launch_wgrad_rows<64, 1>(P, blocks, st) : launch_wgrad_rows<32, 1>(P, blocks, st);
-    else if (Cout == 64) rc = c64 ? launch_wgrad_rows<64, 2>(P, blocks, st) : launch_wgrad_rows<32, 2>(P, blocks, st);
-  } else if (Cout == 32) rc = c64 ? launch_wgrad<64, 1>(P, blocks, st) : launch_wgrad<32, 1>(P, blocks, st);
-  else if (Cout == 64) rc = launch_wgrad<32, 2>(P, blocks, st);        // 32-channel chunks: 5 accumulator tiles per wave, no spills
+  switch ((p.kernel == DU_WGRAD_ROWS ? 1000 : 0) + p.variant) {
+    case 1641: rc = launch_wgrad_rows<64, 1>(P, p.blocks, st); break;
+    case 1321: rc = launch_wgrad_rows<32, 1>(P, p.blocks, st); break;
+    case 1642: rc = launch_wgrad_rows<64, 2>(P, p.blocks, st); break;
+    case 1322: rc = launch_wgrad_rows<32, 2>(P, p.blocks, st); break;
+    case 1324: rc = launch_wgrad_rows<32, 4>(P, p.blocks, st); break;
+    case 641: rc = launch_wgrad<64, 1>(P, p.blocks, st); break;
+    case 321: rc = launch_wgrad<32, 1>(P, p.blocks, st); break;
+    case 322: rc = launch_wgrad<32, 2>(P, p.blocks, st); break;
+  }
   if (rc != DU_OK) return rc;
   // finalize works on (C, 2) pairs: C = elements / 2; with_db the Cout bias-gradient sums ride behind the weight gradient
-  return du_strip_finalize(part, dw, 1, blocks, (Cout * 9 * Cin + (with_db ? Cout : 0)) / 2, stream);
+  return du_strip_finalize(part, dw, 1, p.blocks, (Cout * 9 * Cin + (with_db ? Cout : 0)) / 2, stream);
 }

@@ -29,7 +29,7 @@
 // Roofline: HBM.  Algorithmic bytes per pixel = (Cin + Cout) * 2; 18 MFMAs (576 matrix-pipe cycles) per 4 KB at 32 -> 32.
 #include <stdlib.h>
 #include <utility>
-#include "common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -401,59 +401,49 @@ int strip_launch(const StripParams& P, hipStream_t st) {
   return bias ? go(conv3x3_strip_kernel<NP, NCO, false, true>) : go(conv3x3_strip_kernel<NP, NCO, false, false>);
 }
 
-// segmentation of an image for the strip kernel: rows per segment (0 = shape not served).  Workgroups = B * (W / 128) * (H / RS): two per
-// CU where the image allows it (one per CU for the kernels that keep one workgroup resident), segments of at least 8 rows
-int strip_rows(int B, int H, int W, int want) {
-  if (W % 128 || H % 8) return 0;
-  int rs = H;
-  while (rs >= 16 && rs % 2 == 0 && (long)B * (W / 128) * (H / rs) < want) rs /= 2;
-  return rs;
-}
-bool strip_off() {
-  static const bool off = DU_GETENV("DU_CONV_STRIP") && atoi(DU_GETENV("DU_CONV_STRIP")) == 0;
-  return off;
-}
-// which instantiation serves (C1, Cin, Cout): 0 = none, else NP * 10 + NCO
-int strip_kind(int C1, int Cin, int Cout, bool concat) {
-  if (strip_off() || !(Cout == 32 || Cout == 64)) return 0;
-  if (Cin == 32 && !concat) return 10 + Cout / 32;
-  if (Cin == 64 && (!concat || C1 == 32)) return 20 + Cout / 32;
-  return 0;
-}
-int strip_want(int kind) { return kind == 11 ? 512 : 256; }
-
 }  // namespace
 
-// number of partial-statistics rows du_conv3x3_halo writes for this shape (what the caller allocates: parts x Cout x 2 fp32)
-extern "C" int du_conv3x3_halo_parts(int C1, int Cin, int Cout, int B, int H, int W) {
-  const int kind = strip_kind(C1, Cin, Cout, C1 != Cin);
-  const int rs = kind ? strip_rows(B, H, W, strip_want(kind)) : 0;
-  if (rs) return B * (H / rs) * (W / 32);
-  if (H % 8 || W % 16) return 0;
-  return B * (H / 8) * (W / 16);
+// which instantiation serves (C1, Cin, Cout) on this image: 0 = none, else NP * 10 + NCO, and the segmentation of the image: rows per
+// segment.  Workgroups = B * (W / 128) * (H / rows): two per CU where the image allows it (one per CU for the kernels that keep one
+// workgroup resident), segments of at least 8 rows
+int du_conv3x3_strip_kind(int C1, int Cin, int Cout, bool concat, int B, int H, int W, int* rows) {
+  static const bool off = DU_GETENV("DU_CONV_STRIP") && atoi(DU_GETENV("DU_CONV_STRIP")) == 0;
+  if (off || !(Cout == 32 || Cout == 64) || W % 128 || H % 8) return 0;
+  const int np = Cin == 32 && !concat ? 1 : (Cin == 64 && (!concat || C1 == 32) ? 2 : 0);
+  if (!np) return 0;
+  const int kind = np * 10 + Cout / 32, want = kind == 11 ? 512 : 256;
+  int rs = H;
+  while (rs >= 16 && rs % 2 == 0 && (long)B * (W / 128) * (H / rs) < want) rs /= 2;
+  *rows = rs;
+  return kind;
+}
+// the row DMA addresses one image, the output stores the whole tensor, through 32-bit offsets
+bool du_conv3x3_strip_fits(int B, int H, int W, int64_t ldmax, int64_t ldy) {
+  return (long)H * W * ldmax * 2 < (1L << 30) - 65536 && (long)B * H * W * ldy * 2 < (1L << 31);
 }
 
-// the strip kernel behind du_conv3x3_halo; DU_ERR_UNSUPPORTED = shape not served (the LDS-tiled kernel takes it)
-extern "C" int du_conv3x3_strip(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
-                                const void* w, const float* bias, void* y, int64_t ldy, float* stats_part, void* stream) {
-  if (!x2) C1 = Cin;
-  const int kind = strip_kind(C1, Cin, Cout, x2 != nullptr);
-  const int rs = kind ? strip_rows(B, H, W, strip_want(kind)) : 0;
-  if (!rs) return DU_ERR_UNSUPPORTED;
-  const long ldmax = ldx > ldx2 ? ldx : ldx2;
-  if ((long)H * W * ldmax * 2 >= (1L << 30) - 65536 || (long)B * H * W * ldy * 2 >= (1L << 31)) return DU_ERR_UNSUPPORTED;
+int du_conv3x3_strip_run(const Conv3x3Plan& plan, const void* x, int64_t ldx, const void* x2, int64_t ldx2, int Cout, int B, int H, int W,
+                         const void* w, const float* bias, void* y, int64_t ldy, float* stats_part, void* stream) {
   StripParams P{};
   P.x = (const bf16_t*)x; P.ldx = ldx; P.x2 = (const bf16_t*)x2; P.ldx2 = ldx2; P.w = (const bf16_t*)w; P.bias = bias;
   P.y = (bf16_t*)y; P.ldy = ldy; P.stats_part = stats_part;
   static const int dbg = DU_GETENV("DU_STRIP_DEBUG") ? atoi(DU_GETENV("DU_STRIP_DEBUG")) : 0;
   P.dbg = dbg;
-  P.Cout = Cout; P.B = B; P.H = H; P.W = W; P.RS = rs; P.nseg = H / rs; P.strips = W / 32;
+  P.Cout = Cout; P.B = B; P.H = H; P.W = W; P.RS = plan.strip_rows; P.nseg = H / plan.strip_rows; P.strips = W / 32;
   hipStream_t st = (hipStream_t)stream;
-  switch (kind) {
+  switch (plan.variant) {
     case 11: return strip_launch<1, 1>(P, st);
     case 12: return strip_launch<1, 2>(P, st);
     case 21: return strip_launch<2, 1>(P, st);
     case 22: return strip_launch<2, 2>(P, st);
   }
   return DU_ERR_UNSUPPORTED;
+}
+
+// the strip kernel alone: du_conv3x3_halo for the calls du_conv3x3_plan gives to it, DU_ERR_UNSUPPORTED for every other
+extern "C" int du_conv3x3_strip(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
+                                const void* w, const float* bias, void* y, int64_t ldy, float* stats_part, void* stream) {
+  const Conv3x3Plan p = du_conv3x3_plan(x, ldx, x2, ldx2, C1, Cin, Cout, B, H, W, w, y, ldy, stats_part != nullptr);
+  if (p.kernel != DU_CONV_STRIP) return DU_ERR_UNSUPPORTED;
+  return du_conv3x3_strip_run(p, x, ldx, x2, ldx2, Cout, B, H, W, w, bias, y, ldy, stats_part, stream);
 }

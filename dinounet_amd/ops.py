@@ -975,42 +975,32 @@ def pack_conv_weight_dgrad_flipped(w, dt):
 
 
 def conv3x3_halo(x, wp, bias, x2=None, want_stats=False):
-    """LDS-tiled direct 3x3 / stride 1 / pad 1 convolution (du_conv3x3_halo).  Returns (y, stats_partial or None), or None when the
-    kernel does not serve the shape (caller falls back to the implicit GEMM)."""
+    """Direct 3x3 / stride 1 / pad 1 convolution (du_conv3x3_halo).  Returns (y, stats_partial or None), or None when the library's plan
+    names no kernel (caller falls back to the implicit GEMM).  The plan, asked once, sizes the statistics (no rows: none are emitted)."""
     if x.dtype != torch.bfloat16:
         return None
     B, H, W, C1, ld = _nhwc(x)
     Cout, Kc, ldb = _rows2d(wp)
     Cin = Kc // 9
-    if H % 8 or W % 16 or Cout not in (32, 64, 128) or ldb != Kc or Cin % 32:
+    if ldb != Kc or Kc != 9 * Cin:           # the library takes the packed weight's rows as contiguous
         return None
-    ld2, p2 = 0, None
-    if x2 is not None:
-        B2, H2, W2, C2, ld2 = _nhwc(x2)
-        if (B2, H2, W2) != (B, H, W) or C1 + C2 != Cin or C1 % 32:
-            return None
-        p2 = _p(x2)
-    elif C1 != Cin:
+    C2, ld2 = _nhwc(x2)[3:] if x2 is not None else (0, 0)
+    if C1 + C2 != Cin or (x2 is not None and x2.shape[:3] != x.shape[:3]):
         return None
+    p2 = _p(x2)
     y = torch.empty((B, H, W, Cout), dtype=x.dtype, device=x.device)
-    nparts = int(_lib.lib().du_conv3x3_halo_parts(C1, Cin, Cout, B, H, W)) if want_stats else 0
-    part = torch.empty((nparts, Cout, 2), dtype=torch.float32, device=x.device) if want_stats else None
-    e0 = PROFILE.start() if PROFILE is not None else None
-    rc = _lib.lib().du_conv3x3_halo(_p(x), ld, p2, ld2, C1, Cin, Cout, B, H, W, _p(wp), _p(bias), _p(y), Cout, _p(part), _st())
-    if rc == -2 and part is not None:
-        # the kernel the partial-statistics buffer was sized for declined on the tensor's byte size (ADVICE r4): same convolution without
-        # epilogue statistics (the norm layer then runs its own statistics pass)
-        part = None
-        rc = _lib.lib().du_conv3x3_halo(_p(x), ld, p2, ld2, C1, Cin, Cout, B, H, W, _p(wp), _p(bias), _p(y), Cout, None, _st())
+    L, plan = _lib.lib(), (C.c_int64 * 4)()
+    L.du_conv3x3_plan_describe(_p(x), ld, p2, ld2, C1, Cin, Cout, B, H, W, _p(wp), _p(y), Cout, 1 if want_stats else 0, plan, 4)
+    rc, kernel, _, nparts = plan
     if rc == -2:                                  # DU_ERR_UNSUPPORTED
         return None
-    _lib.check(rc, "du_conv3x3_halo")
+    _lib.check(rc, "du_conv3x3_plan_describe")
+    part = torch.empty((nparts, Cout, 2), dtype=torch.float32, device=x.device) if nparts else None
+    e0 = PROFILE.start() if PROFILE is not None else None
+    _lib.check(L.du_conv3x3_halo(_p(x), ld, p2, ld2, C1, Cin, Cout, B, H, W, _p(wp), _p(bias), _p(y), Cout, _p(part), _st()), "du_conv3x3_halo")
     if PROFILE is not None:
-        # <= 64 output channels: HBM-bound layers (512^2 / 256^2); 128: above the ridge (bench.py reports them against the MFMA peak)
-        # named by the kernel that ran (VERDICT r4 weak 9): the streaming strip kernel writes one partial row per (image, segment, strip),
-        # the LDS-tiled kernel one per 8 x 16 tile -- du_conv3x3_halo_parts tells them apart without mirroring the C-side choice
-        strip = int(_lib.lib().du_conv3x3_halo_parts(C1, Cin, Cout, B, H, W)) != B * (H // 8) * (W // 16)
-        kname = "conv3x3_strip_kernel<bf16>" if strip else ("conv3x3_halo_kernel<bf16>" if Cout <= 64 else "conv3x3_halo_c128_kernel<bf16>")
+        # named by the plan's kernel; the tile kernel's 128-output layers apart: above the ridge (bench.py reports them against the MFMA peak)
+        kname = "conv3x3_strip_kernel<bf16>" if kernel == 1 else ("conv3x3_halo_kernel<bf16>" if Cout <= 64 else "conv3x3_halo_c128_kernel<bf16>")
         PROFILE.stop(kname + (f" {H}x{W} {Cin}->{Cout}" if PROFILE.detail else ""), e0,
                      2.0 * B * H * W * Cin * Cout * 9, 2.0 * B * H * W * (Cin + Cout))
     return y, part
@@ -1088,44 +1078,49 @@ def conv_dgrad(dy, wd, KH, KW, stride, pad, Hin, Win, out=None):
     return out
 
 
-def conv3x3_wgrad_halo(x, dy, x2=None, with_db=False):
-    """LDS-tiled 3x3 / stride 1 / pad 1 weight gradient (du_conv3x3_wgrad_halo) -> fp32 (Cout, 9*Cin), or None if not served.
-    with_db: -> (dw, db): the bias gradient (column sums of dy) rides behind the weight gradient in the same partial slabs."""
-    if x.dtype != torch.bfloat16:
-        return None
+def _wgrad3x3_args(x, dy, x2):
     B, H, W, C1, ld = _nhwc(x)
-    Bo, Ho, Wo, Cout, lddy = _nhwc(dy)
-    Cin, ld2, p2 = C1, 0, None
-    if x2 is not None:
-        _, _, _, C2, ld2 = _nhwc(x2)
-        Cin, p2 = C1 + C2, _p(x2)
-    L = _lib.lib()
-    blocks = int(L.du_conv3x3_wgrad_halo_blocks(C1, Cin, Cout, B, H, W))
-    if blocks <= 0 or (Ho, Wo) != (H, W):
+    C2, ld2 = _nhwc(x2)[3:] if x2 is not None else (0, 0)
+    return _p(x), ld, _p(x2), ld2, C1, C1 + C2, dy.shape[-1], B, H, W, _p(dy), _nhwc(dy)[4]
+
+
+def conv3x3_wgrad_plan(x, dy, x2=None):
+    """du_conv3x3_wgrad_plan_describe for these tensors: [rc, kernel, variant, blocks]; rc -2 = no kernel serves them"""
+    plan = (C.c_int64 * 4)(-2)
+    if x.dtype == torch.bfloat16 and dy.shape[1:3] == x.shape[1:3]:
+        _lib.lib().du_conv3x3_wgrad_plan_describe(*_wgrad3x3_args(x, dy, x2), plan, 4)
+    return plan
+
+
+def conv3x3_wgrad_halo(x, dy, x2=None, with_db=False, plan=None):
+    """LDS-tiled 3x3 / stride 1 / pad 1 weight gradient (du_conv3x3_wgrad_halo) -> fp32 (Cout, 9*Cin), or None if not served.
+    with_db: -> (dw, db): the bias gradient (column sums of dy) rides behind the weight gradient in the same partial slabs.
+    plan: conv3x3_wgrad_plan(x, dy, x2) where the caller has it already."""
+    rc, kernel, _, blocks = plan if plan is not None else conv3x3_wgrad_plan(x, dy, x2)
+    if rc == -2:
         return None
+    _lib.check(rc, "du_conv3x3_wgrad_plan_describe")
+    args = _wgrad3x3_args(x, dy, x2)
+    Cin, Cout, B, H, W = args[5:10]
     nel = Cout * 9 * Cin + (Cout if with_db else 0)
     part = torch.empty((blocks, nel), dtype=torch.float32, device=x.device)
     out = torch.empty(nel, dtype=torch.float32, device=x.device)
     dw = out[:Cout * 9 * Cin].view(Cout, 9 * Cin)
     e0 = PROFILE.start() if PROFILE is not None else None
-    rc = L.du_conv3x3_wgrad_halo(_p(x), ld, p2, ld2, C1, Cin, Cout, B, H, W, _p(dy), lddy, _p(part), _p(out), 1 if with_db else 0, _st())
-    if rc == -2:
-        return None
-    _lib.check(rc, "du_conv3x3_wgrad_halo")
+    _lib.check(_lib.lib().du_conv3x3_wgrad_halo(*args, _p(part), _p(out), 1 if with_db else 0, _st()), "du_conv3x3_wgrad_halo")
     if PROFILE is not None:
-        # (named by the kernel the library runs for this shape: the round-5 rows kernel serves 32 / 64 output channels, conv_halo.hip)
-        wk = "conv3x3_wgrad_rows_kernel<bf16>" if Cout in (32, 64) else "conv3x3_wgrad_halo_kernel<bf16>"
+        wk = "conv3x3_wgrad_rows_kernel<bf16>" if kernel == 1 else "conv3x3_wgrad_halo_kernel<bf16>"
         PROFILE.stop(wk + (f" {H}x{W} {Cin}->{Cout}" if PROFILE.detail else ""), e0,
                      2.0 * B * H * W * Cin * Cout * 9, 2.0 * B * H * W * (Cin + Cout))
     return (dw, out[Cout * 9 * Cin:]) if with_db else dw
 
 
-def conv_wgrad(x, dy, KH, KW, stride, pad, x2=None, with_db=False):
+def conv_wgrad(x, dy, KH, KW, stride, pad, x2=None, with_db=False, plan3x3=None):
     """-> fp32 (Cout, KH*KW*C) in (tap, ci) column order; with_db: -> (dw, db), the bias gradient sum_pixels dy taken inside the
     weight-gradient kernel where it can be (halo kernel: extra slab columns; implicit GEMM: du_gemm_args.a_colsum), else by du_colsum."""
     _req(x, dy)
     if KH == 3 and KW == 3 and stride == 1 and pad == 1:
-        r = conv3x3_wgrad_halo(x, dy, x2, with_db and _WGRAD_COLSUM)
+        r = conv3x3_wgrad_halo(x, dy, x2, with_db and _WGRAD_COLSUM, plan3x3)
         if r is not None:
             if with_db and not _WGRAD_COLSUM:
                 return r, colsum(dy.view(-1, dy.shape[-1]))
@@ -1221,10 +1216,9 @@ class _Conv2d(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             r = None
             Bo, Ho, Wo, Cout, lddy = _nhwc(dy)
-            # 3 x 3 layers the LDS-tiled weight-gradient kernel does not serve (128 output channels): in-place gather on the grouped launch
-            if (KH, KW, stride, pad) == (3, 3, 1, 1) and dy.dtype == torch.bfloat16 and _lib.lib().du_conv3x3_wgrad_halo_blocks(
-                    C1, C1 + (x2.shape[-1] if x2 is not None else 0), Cout, B, Hi, Wi) <= 0 and _pow2(Hi) and _pow2(Wi) and \
-                    (_WGRAD_COLSUM or not want_db):
+            # 3 x 3 layers whose weight-gradient plan (of these tensors) names no kernel (128 output channels): in-place gather on the grouped launch
+            wplan = conv3x3_wgrad_plan(x, dy, x2) if (KH, KW, stride, pad) == (3, 3, 1, 1) else None
+            if wplan is not None and dy.dtype == torch.bfloat16 and wplan[0] != 0 and _pow2(Hi) and _pow2(Wi) and (_WGRAD_COLSUM or not want_db):
                 grp = WGRAD.begin(ctx.wrefs)
                 if grp is not None:
                     srcs = [(x, _nhwc(x)[4], C1)] + ([(x2, _nhwc(x2)[4], x2.shape[-1])] if x2 is not None else [])
@@ -1236,7 +1230,7 @@ class _Conv2d(torch.autograd.Function):
             if r is not None:
                 dw, db = r
             else:
-                g = conv_wgrad(x, dy, KH, KW, stride, pad, x2, with_db=want_db)
+                g = conv_wgrad(x, dy, KH, KW, stride, pad, x2, with_db=want_db, plan3x3=wplan)
                 if want_db:
                     g, db = g
                 dw = g.view(w.shape[0], KH, KW, w.shape[1]).permute(0, 3, 1, 2).contiguous()

@@ -217,26 +217,44 @@ int du_gemm_tn_group(const du_tn_job* jobs, int njobs, void* stream);
 
 /* ---- LDS-tiled direct 3x3 convolution (stride 1, pad 1), bf16 NHWC: decoder / FAPM / SPM-stem convs (dinounet_training.py:581-592,
         dinov3_adapter.py:243-249) and, with flipped + transposed weights, their data gradients --------------------------------------- */
+/* Who decides: du_conv3x3_plan / du_conv3x3_wgrad_plan (csrc/conv_plan.h) choose the kernel, its instantiation, the rows of partial
+   statistics and the number of partial dW slabs, once and before anything launches.  The entries below execute or read those plans, so
+   what du_conv3x3_plan_describe / du_conv3x3_wgrad_plan_describe report for a call is what that call runs. */
 /* x (B,H,W,C1) [+ x2 (B,H,W,Cin-C1): fused concat, nullable]; w bf16 [Cout][9*Cin] in (tap, ci) column order; y (B,H,W,Cout).
-   stats_part (nullable): (du_conv3x3_halo_parts(...), Cout, 2) fp32 partial (sum, sum of squares) of the outputs, the partials of
-   one image contiguous -- feed to du_strip_finalize(G = B).  Returns DU_ERR_UNSUPPORTED for shapes it does not serve (H%8, W%16, Cout not in
-   {32,64,128}, channel counts not multiples of 32): the caller then uses du_gemm's implicit-GEMM path. */
+   stats_part (nullable): (stats_parts of the plan, Cout, 2) fp32 partial (sum, sum of squares) of the outputs, the partials of
+   one image contiguous -- feed to du_strip_finalize(G = B).  Executes the plan: returns its rc -- DU_ERR_UNSUPPORTED for calls no kernel
+   serves (H%8, W%16, Cout not in {32,64,128}, channel counts not multiples of 32, misaligned operands, ...): the caller then uses du_gemm's
+   implicit-GEMM path -- and DU_ERR_UNSUPPORTED for a non-null stats_part where the plan's stats_parts is 0. */
 int du_conv3x3_halo(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
                     const void* w, const float* bias, void* y, int64_t ldy, float* stats_part, void* stream);
-/* rows of the partial-statistics array du_conv3x3_halo writes for this shape (depends on the kernel that serves it; 0 = not served) */
+/* The plan of that call (nothing is dereferenced or launched).  Fills out[0..3], returns 4 (DU_ERR_BAD_ARG: NULL / n < 4): [0] what
+   du_conv3x3_halo would return before any launch (DU_OK, DU_ERR_BAD_ARG, DU_ERR_UNSUPPORTED), [1] kernel: 0 none, 1 conv3x3_strip_kernel,
+   2 conv3x3_halo_kernel, [2] its instantiation: strip NP * 10 + NCO (11, 12, 21, 22), halo CK * 10 + TN (641, 321, 642, 322, 324),
+   [3] stats_parts: rows of the partial-statistics array the kernel writes when want_stats != 0; 0 = the call emits no statistics (a
+   strip shape whose byte sizes the strip kernel declines runs on the tile kernel without them). */
+int du_conv3x3_plan_describe(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
+                             const void* w, const void* y, int64_t ldy, int want_stats, int64_t* out, int n);
+/* A reader of the same plan: stats_parts of the dense, 16-byte aligned call with statistics (pixel strides = channel counts, a second
+   source exactly when C1 != Cin); 0 = not served.  Callers with strided or sliced tensors ask du_conv3x3_plan_describe. */
 int du_conv3x3_halo_parts(int C1, int Cin, int Cout, int B, int H, int W);
-/* The streaming kernel behind du_conv3x3_halo for Cin in {32, 64 (one tensor, or a 32 + 32 concat)}, Cout in {32, 64}, W % 128 == 0,
-   H % 8 == 0 (one wave per 32-column strip, weights in registers / an LDS image, rows by LDS-DMA; csrc/conv_strip.hip).  Arguments as
-   du_conv3x3_halo.  DU_ERR_UNSUPPORTED for any other shape. */
+/* The streaming kernel alone (Cin in {32, 64 (one tensor, or a 32 + 32 concat)}, Cout in {32, 64}, W % 128 == 0, H % 8 == 0: one wave per
+   32-column strip, weights in registers / an LDS image, rows by LDS-DMA; csrc/conv_strip.hip).  Arguments as du_conv3x3_halo; runs the
+   calls whose plan names kernel 1, DU_ERR_UNSUPPORTED for every other. */
 int du_conv3x3_strip(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
                      const void* w, const float* bias, void* y, int64_t ldy, float* stats_part, void* stream);
 /* Weight gradient of the same convolution, dw (Cout, 9*Cin) fp32 in (tap, ci) column order (OVERWRITTEN).  part: scratch of
-   du_conv3x3_wgrad_halo_blocks(...) * Cout * 9*Cin floats (0 blocks = shape not served -> use du_gemm's IM2COL_COL path).
+   (blocks of the plan) * Cout * 9*Cin floats.  Executes the plan: DU_ERR_UNSUPPORTED = not served -> use du_gemm's IM2COL_COL path.
    with_db != 0: the bias gradient db[co] = sum_pixels dy rides along -- dw then has Cout * 9*Cin + Cout elements (db behind the weight
    gradient) and part blocks * (Cout * 9*Cin + Cout). */
-int du_conv3x3_wgrad_halo_blocks(int C1, int Cin, int Cout, int B, int H, int W);
 int du_conv3x3_wgrad_halo(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
                           const void* dy, int64_t lddy, float* part, float* dw, int with_db, void* stream);
+/* The plan of that call.  Fills out[0..3], returns 4 (DU_ERR_BAD_ARG: NULL / n < 4): [0] rc as above, [1] kernel: 0 none,
+   1 conv3x3_wgrad_rows_kernel, 2 the round-3 conv3x3_wgrad_halo_kernel (du_set_option key 13 = 0, or a tensor past the rows kernel's 32-bit
+   offsets, judged on the strides passed), [2] its instantiation CK * 10 + MT, [3] blocks: workgroups = partial dW slabs, keyed on [1]. */
+int du_conv3x3_wgrad_plan_describe(const void* x, int64_t ldx, const void* x2, int64_t ldx2, int C1, int Cin, int Cout, int B, int H, int W,
+                                   const void* dy, int64_t lddy, int64_t* out, int n);
+/* A reader of the same plan: blocks of the dense, 16-byte aligned call (as du_conv3x3_halo_parts); 0 = not served. */
+int du_conv3x3_wgrad_halo_blocks(int C1, int Cin, int Cout, int B, int H, int W);
 /* out[g][c][j] = sum_s part[g*strips + s][c][j]: second stage of the column reductions, exposed for producers that emit partials */
 int du_strip_finalize(const float* part, float* out, int G, int strips, int C, void* stream);
 
