@@ -207,3 +207,5 @@ def predict_sliding_window_logits(net, data, patch_size, tile_step_size=0.5, use
 
 # the export tail (label maps, probabilities, per-case metrics) lives in export.py; its names are part of this module's interface
 from .export import case_metrics, logits_to_segmentation, predict_segmentation  # noqa: E402,F401
+# ... and what precedes the window loop (crop, normalise, resample a raw case) in preprocessing.py: raw array in, label map out
+from .preprocessing import predict_from_raw  # noqa: E402,F401

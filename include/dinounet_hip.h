@@ -704,6 +704,60 @@ int du_cc_label(const uint8_t* seg, int64_t mask_bits, int32_t* ids, int64_t* st
 int du_cc_keep_largest(const uint8_t* seg, int64_t mask_bits, int background_label, uint8_t* out, int64_t* stats, int D, int H, int W,
                        int32_t* ws, int64_t ws_elems, void* stream);
 
+/* ---- preprocessing of a raw case (csrc/preprocess.hip; DefaultPreprocessor.run_case_npy,
+   dinounet/preprocessing/preprocessors/default_preprocessor.py:40-118): crop to the non-zero region, normalise, resample in-plane.  Every
+   launch goes on `stream`; no call reads anything back.
+   du_pre_nonzero_mask: data (C, D, H, W) of dtype DU_PRE_*, read-only -> mask (D, H, W) uint8 = binary_fill_holes(OR_c data[c] != 0) with
+   scipy's default structure: a zero voxel is filled exactly when its 6-connected component of zero voxels touches no face of the volume
+   (so nothing is filled with D <= 2).  bbox (6) int32 DEVICE = {z lo, y lo, x lo, z hi, y hi, x hi}, half open, of the filled mask; hi = 0
+   for an all-zero case.  ws: du_pre_fill_ws_elems(D, H, W) int32 elements, 16-byte aligned = D H W + 1 rounded up to 4: the union-find
+   parents of the zero voxels, shifted by one, word 0 = the node "outside the volume".  Three kernels and two memsets; integer atomics only.
+   DU_ERR_UNSUPPORTED: D H W >= 2^31 - 1 or an unknown dtype.
+   du_pre_crop: one pass over the box [z0, z0 + d) x [y0, y0 + h) x [x0, x0 + w): out (C, d, h, w) fp32 = data converted; seg_out (d, h, w)
+   int16 = with seg (D, H, W) int16: seg, but nonzero_label where seg == 0 outside the mask; without (NULL): nonzero_label outside the
+   mask, 0 inside.
+   du_pre_plane_stats: img (C, D, HW) fp32, seg (D, HW) int16 or NULL -> plane_minmax (C D, 2) fp32 = min and max of every channel slice;
+   chan_stats (C, 5) fp64 = {min, max, sum, count, -} of every channel volume, sum and count over the voxels with seg >= 0 (all voxels
+   without seg), the sum in fp64 in a fixed order.  du_pre_sq_dev: chan_stats[c][4] = the fp64 sum over the same voxels of
+   (x - sum / count)^2, a second pass.  ws of both: du_pre_stats_ws_elems(C, D, HW) fp64 elements.
+   du_pre_normalize: ONE channel volume img (n) fp32 in place, seg (n) int16 or NULL, chan_stats = the 5 doubles of this channel:
+     DU_PRE_NORM_NONE     nothing
+     DU_PRE_NORM_RGB      x / 255 (fp32 divide)
+     DU_PRE_NORM_CT       (min(max(x, p0), p1) - p2) / p3 in fp32, every step rounded (NaN stays NaN)
+     DU_PRE_NORM_RESCALE  (x - min) / max(fp32(max - min), 1e-8f) in fp32
+     DU_PRE_NORM_ZSCORE   fp32((double(x) - mean) / max(std, 1e-8)), mean = sum / count, std = sqrt(sq_dev / count); with seg only where
+                          seg >= 0, every other voxel keeps its bits
+   du_pre_resize_cubic: in (P, H, W) fp32 -> out (P, Ho, Wo) fp32 = skimage.transform.resize(order 3, mode 'edge', anti_aliasing False)
+   of every plane: scipy.ndimage.zoom(order 3, mode 'nearest', grid_mode True), then a clip to bounds (P, 2) fp32 = {lo, hi} of the plane.
+   fp64 throughout, one rounding to fp32.  An axis whose extent does not change is not touched.  tmp: P H Wo fp64 when both axes change,
+   else unused (may be NULL).  DU_ERR_BAD_ARG if neither axis changes.
+   du_pre_resize_seg: in (D, H, W) int16 -> out (D, Ho, Wo) int16 = resize_segmentation(order 1) in integers: the largest label whose
+   bilinear one-hot weight is >= 1/2, else 0. ---- */
+#define DU_PRE_F32 0
+#define DU_PRE_F64 1
+#define DU_PRE_U8 2
+#define DU_PRE_I16 3
+#define DU_PRE_I32 4
+#define DU_PRE_NORM_NONE 0
+#define DU_PRE_NORM_RGB 1
+#define DU_PRE_NORM_CT 2
+#define DU_PRE_NORM_RESCALE 3
+#define DU_PRE_NORM_ZSCORE 4
+int64_t du_pre_fill_ws_elems(int D, int H, int W);
+int du_pre_nonzero_mask(const void* data, int dtype, int C, int D, int H, int W, uint8_t* mask, int32_t* bbox, int32_t* ws,
+                        int64_t ws_elems, void* stream);
+int du_pre_crop(const void* data, int dtype, const uint8_t* mask, const int16_t* seg, int C, int D, int H, int W, int z0, int y0, int x0,
+                int d, int h, int w, int nonzero_label, float* out, int16_t* seg_out, void* stream);
+int64_t du_pre_stats_ws_elems(int C, int D, int64_t HW);
+int du_pre_plane_stats(const float* img, const int16_t* seg, float* plane_minmax, double* chan_stats, int C, int D, int64_t HW, double* ws,
+                       int64_t ws_elems, void* stream);
+int du_pre_sq_dev(const float* img, const int16_t* seg, double* chan_stats, int C, int D, int64_t HW, double* ws, int64_t ws_elems,
+                  void* stream);
+int du_pre_normalize(float* img, const int16_t* seg, const double* chan_stats, int scheme, float p0, float p1, float p2, float p3,
+                     int64_t n, void* stream);
+int du_pre_resize_cubic(const float* in, float* out, const float* bounds, double* tmp, int P, int H, int W, int Ho, int Wo, void* stream);
+int du_pre_resize_seg(const int16_t* in, int16_t* out, int D, int H, int W, int Ho, int Wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
