@@ -1,6 +1,6 @@
 // Band-tiled depthwise 3x3 (stride 1, pad 1) for bf16 channel-last tensors on gfx950: forward, data gradient (with the activation's
 // derivative applied on load) and weight / bias gradient.  Serves ConvFFN's DWConv + GELU over the token pyramid (dinov3_adapter.py:87-109)
-// and DepthwiseSeparableConv.depthwise (dinounet_training.py:235); every shape du_dwconv_band_ok declines stays on elementwise.hip.
+// and DepthwiseSeparableConv.depthwise (dinounet_training.py:235); every call du_dwconv_plan (below; dwconv_plan.h) does not give to them stays on elementwise.hip.
 //
 // Decomposition.  The row kernels of elementwise.hip give a workgroup 32 consecutive pixels of ONE row: rows y - 1 and y + 1 belong to
 // workgroups the dispatcher deals to other XCDs, so every input row is fetched by three L2s and a thread issues 18 loads per 4 outputs.
@@ -16,9 +16,10 @@
 // tap, taps outside the grid contribute x = +0 (an fma with +0 leaves the accumulator as it is), bf16 rounding at the same points.
 // dz = bf16(dy * act'(z)) is formed with act_bwd_kernel's expression.  dw / db are fp32 sums over another partition of the pixels.
 #include "common.h"
+#include "dwconv_plan.h"
 
-int g_dwconv_band = 1;    // du_set_option key 19: 0 = the kernels of elementwise.hip everywhere, 1 = the band kernels where du_dwconv_band_ok
-                          // (default); tuning aid: bits 0-7 >= 2 = bands of that many rows in forward and data gradient, bits 8-15 >= 2 =
+int g_dwconv_band = 1;    // du_set_option key 19: 0 = the kernels of elementwise.hip everywhere, 1 = the band kernels where du_dwconv_plan
+                          // says so (default); tuning aid: bits 0-7 >= 2 = bands of that many rows in forward and data gradient, bits 8-15 >= 2 =
                           // in the weight gradient (0 there: the rule of band_geom)
 
 namespace {
@@ -416,16 +417,10 @@ void band_count(BandGeom& G, int B) {
 
 int band_rows(const BandGeom& G) { return G.row0[G.nlev - 1] + G.nblk[G.nlev - 1]; }
 
-// The geometry of a launch.  Every workgroup walks R rows (plus a prologue worth about a row and a half: item decode, 72 taps, the
-// first three rows), all workgroups start together, and the kernels are bound by their own instructions (the erf of GELU and its
-// derivative: ~550 of the forward's ~800 VALU instructions per row) and by the latency of a row's loads, not by bytes: with 210-230
-// registers two workgroups share a CU, and a launch takes as long as the CU with the most rounds of two.  So R is the band height in
-// 4 .. 16 with the least (workgroups / 512, rounded up) x (R + 1.5): at the token pyramid of the train step 6 rows = 472 workgroups
-// (measured: forward 25.7 us, 8 rows = 336 workgroups 30.1, 11 rows = 256 workgroups 29.0, 16 rows 38.8).
-// rows_cap > 0 (weight gradient): taller bands until at most that many partial rows.
-BandGeom band_geom(int B, int H, int W, int C, int pyramid, long ld, long bs, int rows_cap) {
+// The geometry of a launch with bands of R rows.
+BandGeom band_geom(int B, int H, int W, int C, int pyramid, long ld, long bs, int R) {
   BandGeom G{};
-  G.ld = ld; G.bs = bs; G.C = C;
+  G.ld = ld; G.bs = bs; G.C = C; G.R = R;
   G.nslab = (C + CVB * V - 1) / (CVB * V);
   if (pyramid) {
     const int n = (H * W) >> 2;
@@ -437,6 +432,19 @@ BandGeom band_geom(int B, int H, int W, int C, int pyramid, long ld, long bs, in
     G.nlev = 1;
     G.Hs[0] = H; G.Ws[0] = W; G.s0[0] = 0;
   }
+  band_count(G, B);
+  return G;
+}
+
+// The band height.  Every workgroup walks R rows (plus a prologue worth about a row and a half: item decode, 72 taps, the
+// first three rows), all workgroups start together, and the kernels are bound by their own instructions (the erf of GELU and its
+// derivative: ~550 of the forward's ~800 VALU instructions per row) and by the latency of a row's loads, not by bytes: with 210-230
+// registers two workgroups share a CU, and a launch takes as long as the CU with the most rounds of two.  So R is the band height in
+// 4 .. 16 with the least (workgroups / 512, rounded up) x (R + 1.5): at the token pyramid of the train step 6 rows = 472 workgroups
+// (measured: forward 25.7 us, 8 rows = 336 workgroups 30.1, 11 rows = 256 workgroups 29.0, 16 rows 38.8).
+// rows_cap > 0 (weight gradient): taller bands until at most that many partial rows.
+int band_height(int B, int H, int W, int C, int pyramid, int rows_cap) {
+  BandGeom G = band_geom(B, H, W, C, pyramid, C, 0, 4);
   const int forced = rows_cap > 0 ? (g_dwconv_band >> 8) & 0xff : (g_dwconv_band >= 2 ? g_dwconv_band & 0xff : 0);
   if (forced >= 2) G.R = forced;
   else {
@@ -456,7 +464,7 @@ BandGeom band_geom(int B, int H, int W, int C, int pyramid, long ld, long bs, in
     if (rows_cap <= 0 || band_rows(G) <= rows_cap || G.R >= G.Hs[0]) break;
     G.R *= 2;
   }
-  return G;
+  return G.R;
 }
 
 constexpr int WGRAD_ROWS_CAP = 512;
@@ -468,12 +476,12 @@ void band_forward(const bf16_t* x, const float* w, const float* bias, bf16_t* y,
   else hipLaunchKernelGGL((dwconv_band_kernel<false, -1>), grid, block, 0, st, x, w, bias, y, z, G, act);
 }
 
-int band_backward(const bf16_t* z, const bf16_t* dy, const bf16_t* x, const float* w, bf16_t* dx, float* dw, float* db, bf16_t* dz, int B,
-                  int H, int W, int C, int pyramid, long ld, long bs, int act, float* ws, int64_t ws_elems, int accumulate, hipStream_t st) {
-  const BandGeom G = band_geom(B, H, W, C, pyramid, ld, bs, 0);
+// data gradient (the activation's derivative on load: dz is written for the weight gradient), weight gradient, second stage
+void band_backward(const DwconvPlan& plan, const bf16_t* z, const bf16_t* dy, const bf16_t* x, const float* w, bf16_t* dx, float* dw,
+                   float* db, bf16_t* dz, int B, int H, int W, int C, int pyramid, long ld, long bs, int act, float* ws, hipStream_t st) {
+  const BandGeom G = band_geom(B, H, W, C, pyramid, ld, bs, plan.R);
   const bf16_t* g = dy;
-  if (act != DU_ACT_NONE) {
-    if (!z || !dz) return DU_ERR_BAD_ARG;
+  if (plan.act_bwd == DU_DW_ACT_ON_LOAD) {
     bool cut = false;                          // a row shared by two workgroups
     for (int l = 0; l < G.nlev; l++) cut = cut || NL % G.ncg[l] != 0;
     const dim3 grid(G.wg0[G.nlev]), block(256);
@@ -485,52 +493,105 @@ int band_backward(const bf16_t* z, const bf16_t* dy, const bf16_t* x, const floa
     hipLaunchKernelGGL((dwconv_band_kernel<true, DU_ACT_NONE>), dim3(G.wg0[G.nlev]), dim3(256), 0, st, dy, w, (const float*)nullptr, dx,
                        (bf16_t*)nullptr, G, (int)DU_ACT_NONE);
   }
-  const BandGeom GW = band_geom(B, H, W, C, pyramid, ld, bs, WGRAD_ROWS_CAP);
-  const int rows = band_rows(GW);
-  if (!ws || ws_elems < (int64_t)rows * 10 * C) return DU_ERR_BAD_ARG;
+  const BandGeom GW = band_geom(B, H, W, C, pyramid, ld, bs, plan.wgrad_R);
   hipLaunchKernelGGL(dwconv_band_wgrad_kernel, dim3(GW.wg0[GW.nlev]), dim3(256), 0, st, x, g, ws, GW);
-  hipLaunchKernelGGL(dwconv_band_finalize_kernel, dim3((C * 10 + 31) / 32), dim3(256), 0, st, (const float*)ws, dw, db, rows, C, accumulate);
-  return du_check_launch();
+  hipLaunchKernelGGL(dwconv_band_finalize_kernel, dim3((C * 10 + 31) / 32), dim3(256), 0, st, (const float*)ws, dw, db, plan.rows, C, 0);
+}
+
+// the 4-pixel row kernels need every grid of the token pyramid -- widths 2W, W, W / 2 -- to be a multiple of 4
+bool row4_ok(int W) {
+  static const bool off = DU_GETENV("DU_DWCONV_NO_ROW4") != nullptr;      // debugging / A-B aid
+  return !off && W % 8 == 0;
+}
+
+// pixels per workgroup of the row family's weight gradient
+int row_wgrad_strip(long npix, int C, int v) {
+  // ~512 workgroups per launch, but at least 4 pixels per pixel lane so the LDS reduction stays amortised
+  const int cvb = (C / v) < 256 ? (C / v) : 256;
+  const int np = 256 / cvb;
+  long strip = (npix + 511) / 512;           // 512 strips: the partial buffer the finalize kernel re-reads halves (measured vs 1024)
+  if (strip < (long)np * 4) strip = (long)np * 4;
+  return (int)((strip + 3) / 4 * 4);         // whole 4-pixel groups (row form of the kernel)
 }
 
 }  // namespace
 
-extern "C" int du_dwconv_band_ok(int dtype, int B, int H, int W, int C, int pyramid) { return band_shape_ok(dtype, B, H, W, C, pyramid) ? 1 : 0; }
-
-extern "C" int64_t du_dwconv_band_ws_elems(int dtype, int B, int H, int W, int C, int pyramid) {
-  if (!band_shape_ok(dtype, B, H, W, C, pyramid)) return 0;
-  return (int64_t)band_rows(band_geom(B, H, W, C, pyramid, C, 0, WGRAD_ROWS_CAP)) * 10 * C;
+DwconvPlan du_dwconv_plan(int dtype, int64_t ld, int64_t bs, int B, int H, int W, int C, int pyramid, int act) {
+  DwconvPlan p{};
+  p.rc = DU_ERR_BAD_ARG;
+  const int v = dtype == DU_BF16 ? 8 : 4;
+  if ((dtype != DU_BF16 && dtype != DU_F32) || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % v) return p;
+  const long pix = pyramid ? 21L * (((long)H * W) >> 2) : (long)H * W;      // of one image
+  const bool dense = ld == C && bs == pix * C;
+  p.act_bwd = act == DU_ACT_NONE ? DU_DW_ACT_NONE : DU_DW_ACT_PASS;
+  if (band_shape_ok(dtype, B, H, W, C, pyramid) && ld % V == 0 && bs % V == 0 && (pyramid || act == DU_ACT_NONE)) {
+    p.kernel = DU_DW_BAND;
+    p.R = band_height(B, H, W, C, pyramid, 0);
+    if (act != DU_ACT_NONE) p.act_bwd = DU_DW_ACT_ON_LOAD;
+    p.wgrad = DU_DWW_BAND;
+    p.wgrad_R = band_height(B, H, W, C, pyramid, WGRAD_ROWS_CAP);
+    p.rows = band_rows(band_geom(B, H, W, C, pyramid, ld, bs, p.wgrad_R));      // one per item block: its slabs share the row
+    p.ws_elems = (int64_t)p.rows * 10 * C;
+    p.rc = pyramid && !dense ? DU_ERR_BAD_ARG : DU_OK;
+    return p;
+  }
+  const bool four = pyramid && dtype == DU_BF16 && row4_ok(W);
+  p.kernel = four ? DU_DW_ROW4 : DU_DW_ROW;
+  p.strip = row_wgrad_strip((long)B * pix, C, v);
+  p.wgrad = !pyramid ? DU_DWW_ROW : (four && p.strip % 4 == 0 ? DU_DWW_PYR_ROW4 : DU_DWW_PYR);
+  p.rows = (int)(((long)B * pix + p.strip - 1) / p.strip);
+  p.ws_elems = (int64_t)p.rows * 10 * C;
+  if (ld % v || bs % v || (pyramid && ((H & 1) || (W & 1) || !dense))) p.rc = DU_ERR_BAD_ARG;
+  else if (act != DU_ACT_NONE && !dense) p.rc = DU_ERR_UNSUPPORTED;      // act_bwd_kernel is one launch over contiguous elements
+  else p.rc = DU_OK;
+  return p;
 }
 
-extern "C" int du_dwconv_band_tokens_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, void* z, int B, int H, int W,
-                                         int C, int act, void* stream) {
-  if (!x || !w || !y || !band_shape_ok(dtype, B, H, W, C, 1)) return DU_ERR_BAD_ARG;
-  const long N = 21L * ((H * W) >> 2);
-  const BandGeom G = band_geom(B, H, W, C, 1, C, N * C, 0);
-  band_forward((const bf16_t*)x, w, bias, (bf16_t*)y, (bf16_t*)z, G, act, (hipStream_t)stream);
+extern "C" int du_dwconv3x3_plan_describe(int dtype, int64_t ld, int64_t bs, int B, int H, int W, int C, int pyramid, int act, int64_t* out,
+                                          int n) {
+  if (!out || n < 7) return DU_ERR_BAD_ARG;
+  const DwconvPlan p = du_dwconv_plan(dtype, ld, bs, B, H, W, C, pyramid, act);
+  out[0] = p.rc; out[1] = p.kernel; out[2] = p.R; out[3] = p.act_bwd; out[4] = p.wgrad; out[5] = p.rows; out[6] = p.ws_elems;
+  return 7;
+}
+
+extern "C" int64_t du_dwconv3x3_bwd_ws_elems(int dtype, int64_t ld, int64_t bs, int B, int H, int W, int C, int pyramid, int act) {
+  return du_dwconv_plan(dtype, ld, bs, B, H, W, C, pyramid, act).ws_elems;
+}
+
+extern "C" int du_dwconv3x3_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, void* z, int64_t ld, int64_t bs, int B,
+                                int H, int W, int C, int pyramid, int act, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const DwconvPlan p = du_dwconv_plan(dtype, ld, bs, B, H, W, C, pyramid, act);
+  if (p.rc != DU_OK) return p.rc;
+  if (!x || !w || !y) return DU_ERR_BAD_ARG;
+  if (p.kernel == DU_DW_BAND)
+    band_forward((const bf16_t*)x, w, bias, (bf16_t*)y, (bf16_t*)z, band_geom(B, H, W, C, pyramid, ld, bs, p.R), act, st);
+  else du_dwconv_row_run(p, dtype, x, w, bias, y, z, ld, bs, B, H, W, C, pyramid, act, false, st);
   return du_check_launch();
 }
 
-extern "C" int du_dwconv_band_tokens_bwd(int dtype, const void* z, const void* dy, const void* x, const float* w, void* dx, float* dw,
-                                         float* db, void* dz, int B, int H, int W, int C, int act, float* ws, int64_t ws_elems,
-                                         void* stream) {
-  if (!dy || !x || !w || !dx || !dw || !band_shape_ok(dtype, B, H, W, C, 1)) return DU_ERR_BAD_ARG;
-  const long N = 21L * ((H * W) >> 2);
-  return band_backward((const bf16_t*)z, (const bf16_t*)dy, (const bf16_t*)x, w, (bf16_t*)dx, dw, db, (bf16_t*)dz, B, H, W, C, 1, C, N * C, act,
-                       ws, ws_elems, 0, (hipStream_t)stream);
-}
-
-extern "C" int du_dwconv_band_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, int64_t ld, int64_t bs, int B, int H,
-                                  int W, int C, void* stream) {
-  if (!x || !w || !y || ld % V || bs % V || !band_shape_ok(dtype, B, H, W, C, 0)) return DU_ERR_BAD_ARG;
-  const BandGeom G = band_geom(B, H, W, C, 0, ld, bs, 0);
-  band_forward((const bf16_t*)x, w, bias, (bf16_t*)y, (bf16_t*)nullptr, G, DU_ACT_NONE, (hipStream_t)stream);
+extern "C" int du_dwconv3x3_bwd(int dtype, const void* z, const void* dy, const void* x, const float* w, void* dx, float* dw, float* db,
+                                void* dz, int64_t ld, int64_t bs, int B, int H, int W, int C, int pyramid, int act, float* ws,
+                                int64_t ws_elems, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const DwconvPlan p = du_dwconv_plan(dtype, ld, bs, B, H, W, C, pyramid, act);
+  if (p.rc != DU_OK) return p.rc;
+  if (!dy || !x || !w || !dx || !dw || !ws || ws_elems < p.ws_elems) return DU_ERR_BAD_ARG;
+  if (p.act_bwd != DU_DW_ACT_NONE && (!z || !dz)) return DU_ERR_BAD_ARG;
+  if (p.kernel == DU_DW_BAND) {
+    band_backward(p, (const bf16_t*)z, (const bf16_t*)dy, (const bf16_t*)x, w, (bf16_t*)dx, dw, db, (bf16_t*)dz, B, H, W, C, pyramid, ld, bs,
+                  act, ws, st);
+    return du_check_launch();
+  }
+  const void* g = dy;
+  if (p.act_bwd == DU_DW_ACT_PASS) {
+    const long pix = pyramid ? 21L * (((long)H * W) >> 2) : (long)H * W;
+    const int rc = du_act_bwd(dtype, z, dy, dz, (int64_t)B * pix * C, act, stream);
+    if (rc != DU_OK) return rc;
+    g = dz;
+  }
+  du_dwconv_row_run(p, dtype, g, w, nullptr, dx, nullptr, ld, bs, B, H, W, C, pyramid, DU_ACT_NONE, true, st);
+  du_dwconv_row_wgrad(p, dtype, x, g, dw, db, ld, bs, B, H, W, C, ws, st);
   return du_check_launch();
-}
-
-extern "C" int du_dwconv_band_bwd(int dtype, const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, int64_t ld,
-                                  int64_t bs, int B, int H, int W, int C, float* ws, int64_t ws_elems, int accumulate, void* stream) {
-  if (!dy || !x || !w || !dx || !dw || ld % V || bs % V || !band_shape_ok(dtype, B, H, W, C, 0)) return DU_ERR_BAD_ARG;
-  return band_backward(nullptr, (const bf16_t*)dy, (const bf16_t*)x, w, (bf16_t*)dx, dw, db, nullptr, B, H, W, C, 0, ld, bs, DU_ACT_NONE, ws,
-                       ws_elems, accumulate, (hipStream_t)stream);
 }

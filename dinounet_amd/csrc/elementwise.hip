@@ -2,6 +2,7 @@
 // MSDeformAttn sampling-location / softmax preparation.  All use 16-byte channel vectors per thread.
 #include <stdlib.h>
 #include "common.h"
+#include "dwconv_plan.h"
 
 namespace {
 
@@ -859,130 +860,56 @@ static inline int dwconv_grid(long npix, int C, int v) {
   return (int)(blocks < 1 ? 1 : blocks);
 }
 
-extern "C" int du_dwconv3x3_fwd(int dtype, const void* x, int64_t ldx, int64_t xbs, const float* w, const float* bias, void* y,
-                                int64_t ldy, int64_t ybs, void* z, int B, int H, int W, int C, int act, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int v = dtype == DU_BF16 ? 8 : 4;
-  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || C % v || ldx % v || ldy % v || xbs % v || ybs % v) return DU_ERR_BAD_ARG;
-  const int grid = dwconv_grid((long)B * H * W, C, v);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((dwconv_kernel<bf16_t, false, false>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, ldx, xbs, w, bias, (bf16_t*)y, ldy, ybs, (bf16_t*)z, B, H, W, C, act, 0),
-             hipLaunchKernelGGL((dwconv_kernel<float, false, false>), dim3(grid), dim3(256), 0, st, (const float*)x, ldx, xbs, w, bias, (float*)y, ldy, ybs, (float*)z, B, H, W, C, act, 0));
-  return du_check_launch();
-}
+// ---- the row family of the depthwise 3x3: launchers of a DwconvPlan (dwconv_plan.h; du_dwconv_plan in dwconv.hip decides) ----
+// pixels of the call: one NHWC segment, or the (B, 21 n, C) token pyramid of ConvFFN (dinov3_adapter.py:99-109), one launch either way
+static inline long dwconv_npix(int B, int H, int W, int pyramid) { return (long)B * (pyramid ? 21L * (((long)H * W) >> 2) : (long)H * W); }
 
-extern "C" int du_dwconv3x3_bwd_data(int dtype, const void* dy, int64_t lddy, int64_t dybs, const float* w, void* dx, int64_t lddx,
-                                     int64_t dxbs, int B, int H, int W, int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int v = dtype == DU_BF16 ? 8 : 4;
-  if (!dy || !w || !dx || B <= 0 || C % v || lddy % v || lddx % v || dybs % v || dxbs % v) return DU_ERR_BAD_ARG;
-  const int grid = dwconv_grid((long)B * H * W, C, v);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((dwconv_kernel<bf16_t, true, false>), dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, lddy, dybs, w, (const float*)nullptr, (bf16_t*)dx, lddx, dxbs, (bf16_t*)nullptr, B, H, W, C, DU_ACT_NONE, 0),
-             hipLaunchKernelGGL((dwconv_kernel<float, true, false>), dim3(grid), dim3(256), 0, st, (const float*)dy, lddy, dybs, w, (const float*)nullptr, (float*)dx, lddx, dxbs, (float*)nullptr, B, H, W, C, DU_ACT_NONE, 0));
-  return du_check_launch();
-}
-
-// the row forms (4 consecutive pixels of a row per thread) need every grid of the token pyramid -- widths 2W, W, W / 2 -- to be a multiple of 4
-static inline bool dwconv_row4_ok(int W) {
-  static const bool off = DU_GETENV("DU_DWCONV_NO_ROW4") != nullptr;      // debugging / A-B aid
-  return !off && W % 8 == 0;
-}
-
-static inline int dwconv_wgrad_strip(long npix, int C, int v) {
-  // ~512 workgroups per launch, but at least 4 pixels per pixel lane so the LDS reduction stays amortised
-  const int cvb_ = (C / v) < 256 ? (C / v) : 256;
-  const int np_ = 256 / cvb_;
-  long strip_l = (npix + 511) / 512;        // 512 strips: the partial buffer the finalize kernel re-reads halves (measured vs 1024)
-  if (strip_l < (long)np_ * 4) strip_l = (long)np_ * 4;
-  strip_l = (strip_l + 3) / 4 * 4;          // whole 4-pixel groups (row form of the kernel)
-  return (int)strip_l;
-}
-
-extern "C" int64_t du_dwconv_wgrad_ws_elems(int dtype, int B, int H, int W, int C) {
-  const int v = dtype == DU_BF16 ? 8 : 4;
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % v) return 0;
-  const long npix = (long)B * H * W;
-  const int strip = dwconv_wgrad_strip(npix, C, v);
-  return (int64_t)((npix + strip - 1) / strip) * C * 10;
-}
-
-extern "C" int du_dwconv3x3_bwd_weight(int dtype, const void* x, int64_t ldx, int64_t xbs, const void* dy, int64_t lddy, int64_t dybs,
-                                       float* dw, float* db, int B, int H, int W, int C, float* ws, int64_t ws_elems, int accumulate,
-                                       void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int v = dtype == DU_BF16 ? 8 : 4;
-  if (!x || !dy || !dw || B <= 0 || C % v || ldx % v || lddy % v || xbs % v || dybs % v) return DU_ERR_BAD_ARG;
-  const long npix = (long)B * H * W;
-  const int strip = dwconv_wgrad_strip(npix, C, v);
-  long blocks = (npix + strip - 1) / strip;
-  float* part = (ws && ws_elems >= blocks * C * 10) ? ws : nullptr;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((dwconv_bwd_weight_kernel<bf16_t, false>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, ldx, xbs, (const bf16_t*)dy, lddy, dybs, dw, db, B, H, W, C, strip, part),
-             hipLaunchKernelGGL((dwconv_bwd_weight_kernel<float, false>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, ldx, xbs, (const float*)dy, lddy, dybs, dw, db, B, H, W, C, strip, part));
-  if (part)
-    hipLaunchKernelGGL(dwconv_wgrad_finalize_kernel, dim3((C * 10 + 31) / 32), dim3(256), 0, st, (const float*)part, dw, db, (int)blocks, C, accumulate);
-  return du_check_launch();
-}
-
-// ---- the same three kernels over the (B, 21 n, C) token pyramid of ConvFFN (dinov3_adapter.py:99-109), one launch each ----
-extern "C" int du_dwconv3x3_tokens_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, void* z, int B, int H,
-                                       int W, int C, int act, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int v = dtype == DU_BF16 ? 8 : 4;
-  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C % v) return DU_ERR_BAD_ARG;
-  const long N = 21L * ((H * W) >> 2);
-  if (dwconv_row4_ok(W) && dtype == DU_BF16) {       // W / 2 (the narrowest grid) % 4 == 0: 4 outputs per thread (dwconv_row4_kernel)
-    const int grid4 = dwconv_grid((long)B * N / 4, C, v);
-    hipLaunchKernelGGL((dwconv_row4_kernel<bf16_t, false, true>), dim3(grid4), dim3(256), 0, st, (const bf16_t*)x, (long)C, N * C, w, bias, (bf16_t*)y, (long)C, N * C, (bf16_t*)z, B, H, W, C, act);
-    return du_check_launch();
+template <typename T, bool FLIP>
+static void dwconv_row_launch(const DwconvPlan& plan, const T* x, const float* w, const float* bias, T* y, T* z, long ld, long bs, int B,
+                              int H, int W, int C, int pyramid, int act, hipStream_t st) {
+  constexpr int v = Elem<T>::VEC;
+  const long npix = dwconv_npix(B, H, W, pyramid);
+  if constexpr (Elem<T>::DT == DU_BF16) {
+    if (plan.kernel == DU_DW_ROW4) {       // every grid width of the pyramid a multiple of 4: 4 outputs per thread
+      hipLaunchKernelGGL((dwconv_row4_kernel<T, FLIP, true>), dim3(dwconv_grid(npix / 4, C, v)), dim3(256), 0, st, x, ld, bs, w, bias, y, ld, bs, z, B, H, W, C, act);
+      return;
+    }
   }
-  const int grid = dwconv_grid((long)B * N, C, v);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((dwconv_kernel<bf16_t, false, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (long)C, N * C, w, bias, (bf16_t*)y, (long)C, N * C, (bf16_t*)z, B, H, W, C, act, 0),
-             hipLaunchKernelGGL((dwconv_kernel<float, false, true>), dim3(grid), dim3(256), 0, st, (const float*)x, (long)C, N * C, w, bias, (float*)y, (long)C, N * C, (float*)z, B, H, W, C, act, 0));
-  return du_check_launch();
+  const dim3 grid(dwconv_grid(npix, C, v));
+  if (pyramid) hipLaunchKernelGGL((dwconv_kernel<T, FLIP, true>), grid, dim3(256), 0, st, x, ld, bs, w, bias, y, ld, bs, z, B, H, W, C, act, 0);
+  else hipLaunchKernelGGL((dwconv_kernel<T, FLIP, false>), grid, dim3(256), 0, st, x, ld, bs, w, bias, y, ld, bs, z, B, H, W, C, act, 0);
 }
 
-extern "C" int du_dwconv3x3_tokens_bwd_data(int dtype, const void* dy, const float* w, void* dx, int B, int H, int W, int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int v = dtype == DU_BF16 ? 8 : 4;
-  if (!dy || !w || !dx || B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C % v) return DU_ERR_BAD_ARG;
-  const long N = 21L * ((H * W) >> 2);
-  if (dwconv_row4_ok(W) && dtype == DU_BF16) {
-    const int grid4 = dwconv_grid((long)B * N / 4, C, v);
-    hipLaunchKernelGGL((dwconv_row4_kernel<bf16_t, true, true>), dim3(grid4), dim3(256), 0, st, (const bf16_t*)dy, (long)C, N * C, w, (const float*)nullptr, (bf16_t*)dx, (long)C, N * C, (bf16_t*)nullptr, B, H, W, C, DU_ACT_NONE);
-    return du_check_launch();
+void du_dwconv_row_run(const DwconvPlan& plan, int dtype, const void* x, const float* w, const float* bias, void* y, void* z, int64_t ld,
+                       int64_t bs, int B, int H, int W, int C, int pyramid, int act, bool flip, hipStream_t st) {
+  if (dtype == DU_BF16) {
+    if (flip) dwconv_row_launch<bf16_t, true>(plan, (const bf16_t*)x, w, bias, (bf16_t*)y, (bf16_t*)z, ld, bs, B, H, W, C, pyramid, act, st);
+    else dwconv_row_launch<bf16_t, false>(plan, (const bf16_t*)x, w, bias, (bf16_t*)y, (bf16_t*)z, ld, bs, B, H, W, C, pyramid, act, st);
+  } else {
+    if (flip) dwconv_row_launch<float, true>(plan, (const float*)x, w, bias, (float*)y, (float*)z, ld, bs, B, H, W, C, pyramid, act, st);
+    else dwconv_row_launch<float, false>(plan, (const float*)x, w, bias, (float*)y, (float*)z, ld, bs, B, H, W, C, pyramid, act, st);
   }
-  const int grid = dwconv_grid((long)B * N, C, v);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((dwconv_kernel<bf16_t, true, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, (long)C, N * C, w, (const float*)nullptr, (bf16_t*)dx, (long)C, N * C, (bf16_t*)nullptr, B, H, W, C, DU_ACT_NONE, 0),
-             hipLaunchKernelGGL((dwconv_kernel<float, true, true>), dim3(grid), dim3(256), 0, st, (const float*)dy, (long)C, N * C, w, (const float*)nullptr, (float*)dx, (long)C, N * C, (float*)nullptr, B, H, W, C, DU_ACT_NONE, 0));
-  return du_check_launch();
 }
 
-// scratch: du_dwconv_wgrad_ws_elems(dtype, B, 21 * H * W / 4, 1, C) floats
-extern "C" int du_dwconv3x3_tokens_bwd_weight(int dtype, const void* x, const void* dy, float* dw, float* db, int B, int H, int W, int C,
-                                              float* ws, int64_t ws_elems, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int v = dtype == DU_BF16 ? 8 : 4;
-  if (!x || !dy || !dw || B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C % v) return DU_ERR_BAD_ARG;
-  const long N = 21L * ((H * W) >> 2);
-  const long npix = (long)B * N;
-  const int strip = dwconv_wgrad_strip(npix, C, v);
-  long blocks = (npix + strip - 1) / strip;
-  float* part = (ws && ws_elems >= blocks * C * 10) ? ws : nullptr;
-  if (!part) return DU_ERR_BAD_ARG;          // the partial + finalize form overwrites dw / db: no zero-fill contract on this entry point
-  if (dwconv_row4_ok(W) && dtype == DU_BF16 && strip % 4 == 0) {
-    hipLaunchKernelGGL((dwconv_bwd_weight_kernel<bf16_t, true, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, (long)C, N * C, (const bf16_t*)dy, (long)C, N * C, dw, db, B, H, W, C, strip, part);
-    hipLaunchKernelGGL(dwconv_wgrad_finalize_kernel, dim3((C * 10 + 31) / 32), dim3(256), 0, st, (const float*)part, dw, db, (int)blocks, C, 0);
-    return du_check_launch();
+template <typename T>
+static void dwconv_row_wgrad_launch(const DwconvPlan& plan, const T* x, const T* dz, float* dw, float* db, long ld, long bs, int B, int H,
+                                    int W, int C, float* part, hipStream_t st) {
+  const dim3 grid((unsigned)plan.rows), block(256);
+  if constexpr (Elem<T>::DT == DU_BF16) {
+    if (plan.wgrad == DU_DWW_PYR_ROW4) {
+      hipLaunchKernelGGL((dwconv_bwd_weight_kernel<T, true, true>), grid, block, 0, st, x, ld, bs, dz, ld, bs, dw, db, B, H, W, C, plan.strip, part);
+      return;
+    }
   }
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((dwconv_bwd_weight_kernel<bf16_t, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, (long)C, N * C, (const bf16_t*)dy, (long)C, N * C, dw, db, B, H, W, C, strip, part),
-             hipLaunchKernelGGL((dwconv_bwd_weight_kernel<float, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, (long)C, N * C, (const float*)dy, (long)C, N * C, dw, db, B, H, W, C, strip, part));
-  hipLaunchKernelGGL(dwconv_wgrad_finalize_kernel, dim3((C * 10 + 31) / 32), dim3(256), 0, st, (const float*)part, dw, db, (int)blocks, C, 0);
-  return du_check_launch();
+  if (plan.wgrad == DU_DWW_PYR) hipLaunchKernelGGL((dwconv_bwd_weight_kernel<T, true>), grid, block, 0, st, x, ld, bs, dz, ld, bs, dw, db, B, H, W, C, plan.strip, part);
+  else hipLaunchKernelGGL((dwconv_bwd_weight_kernel<T, false>), grid, block, 0, st, x, ld, bs, dz, ld, bs, dw, db, B, H, W, C, plan.strip, part);
+}
+
+void du_dwconv_row_wgrad(const DwconvPlan& plan, int dtype, const void* x, const void* dz, float* dw, float* db, int64_t ld, int64_t bs,
+                         int B, int H, int W, int C, float* part, hipStream_t st) {
+  if (dtype == DU_BF16) dwconv_row_wgrad_launch<bf16_t>(plan, (const bf16_t*)x, (const bf16_t*)dz, dw, db, ld, bs, B, H, W, C, part, st);
+  else dwconv_row_wgrad_launch<float>(plan, (const float*)x, (const float*)dz, dw, db, ld, bs, B, H, W, C, part, st);
+  hipLaunchKernelGGL(dwconv_wgrad_finalize_kernel, dim3((C * 10 + 31) / 32), dim3(256), 0, st, (const float*)part, dw, db, plan.rows, C, 0);
 }
 
 extern "C" int du_maxpool3x3s2_fwd(int dtype, const void* x, void* y, uint8_t* idx, int B, int H, int W, int C, void* stream) {

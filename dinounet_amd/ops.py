@@ -2008,132 +2008,69 @@ def offsets_prep(x, w1, w2, b1, b2, ref, Lq, M, P, Hs, Ws):
 # ----------------------------------------------------------------------------------------------------
 # small NHWC ops
 # ----------------------------------------------------------------------------------------------------
-class _DWConvSegs(torch.autograd.Function):
-    """Depthwise 3x3 (+bias, +activation) over one or more image segments of a flat channel-last tensor.
-    seg = (element offset, B, H, W, pixel stride ld, per-image stride bs).  Serves plain NHWC tensors
-    (dinounet_training.py:235) and ConvFFN's DWConv (dinov3_adapter.py:99-109): one depthwise kernel applied to the
-    three token ranges of a (B, N, C) tensor viewed as (2H x 2W), (H x W), (H/2 x W/2) grids, then GELU (:87)."""
+def _dwconv_fwd(ctx, x, w, bias, geom, act):
+    """geom = (pixel stride, image stride, B, H, W, pyramid) of du_dwconv3x3_fwd: the library picks the kernel (csrc/dwconv_plan.h)"""
+    x = x.contiguous()
+    Cc = w.shape[0]
+    wf = _f32(w).view(Cc, 9)
+    y = torch.empty_like(x)
+    z = torch.empty_like(x) if act != ACT_NONE else None
+    ld, bs, B, H, W, pyramid = geom
+    _lib.check(_lib.lib().du_dwconv3x3_fwd(_code(x.dtype), _p(x), _p(wf), _p(_f32(bias)), _p(y), _p(z), ld, bs, B, H, W, Cc, pyramid, act, _st()),
+               "du_dwconv3x3_fwd")
+    ctx.save_for_backward(x, wf, z)
+    ctx.conf = (geom, act, bias is not None)
+    return y
+
+
+def _dwconv_bwd(ctx, dy):
+    x, wf, z = ctx.saved_tensors
+    (ld, bs, B, H, W, pyramid), act, has_bias = ctx.conf
+    Cc = wf.shape[0]
+    L = _lib.lib()
+    code = _code(x.dtype)
+    dy = dy.contiguous()
+    dz = torch.empty_like(dy) if act != ACT_NONE else None      # scratch: dy * act'(z)
+    dx = torch.empty_like(x)
+    dw = torch.empty((Cc, 9), dtype=torch.float32, device=x.device)
+    db = torch.empty(Cc, dtype=torch.float32, device=x.device) if has_bias else None
+    n = int(L.du_dwconv3x3_bwd_ws_elems(code, ld, bs, B, H, W, Cc, pyramid, act))
+    ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
+    _lib.check(L.du_dwconv3x3_bwd(code, _p(z), _p(dy), _p(x), _p(wf), _p(dx), _p(dw), _p(db), _p(dz), ld, bs, B, H, W, Cc, pyramid, act,
+                                  _p(ws), n, _st()), "du_dwconv3x3_bwd")
+    return dx, dw.view(Cc, 1, 3, 3), db
+
+
+class _DWConv(torch.autograd.Function):
+    """Depthwise 3x3 (+bias, +activation) over a contiguous NHWC tensor (dinounet_training.py:235)."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, segs, act):
-        x = x.contiguous()
-        Cc = w.shape[0]
-        wf = _f32(w).view(Cc, 9)
-        bf = _f32(bias)
-        y = torch.empty_like(x)
-        z = torch.empty_like(x) if act != ACT_NONE else None
-        es = x.element_size()
-        L = _lib.lib()
-        for (off, B, h, ww, ld, bs) in segs:
-            if act == ACT_NONE and L.du_dwconv_band_ok(_code(x.dtype), B, h, ww, Cc, 0):      # band kernels (csrc/dwconv.hip)
-                _lib.check(L.du_dwconv_band_fwd(_code(x.dtype), C.c_void_p(x.data_ptr() + off * es), _p(wf), _p(bf),
-                                                C.c_void_p(y.data_ptr() + off * es), ld, bs, B, h, ww, Cc, _st()), "du_dwconv_band_fwd")
-                continue
-            _lib.check(L.du_dwconv3x3_fwd(_code(x.dtype), C.c_void_p(x.data_ptr() + off * es), ld, bs, _p(wf), _p(bf),
-                                          C.c_void_p(y.data_ptr() + off * es), ld, bs,
-                                          None if z is None else C.c_void_p(z.data_ptr() + off * es), B, h, ww, Cc, act, _st()),
-                       "du_dwconv3x3_fwd")
-        ctx.save_for_backward(x, wf, z)
-        ctx.conf = (segs, act, bias is not None, Cc)
-        return y
+    def forward(ctx, x, w, bias, act):
+        B, H, W, Cc = x.shape
+        return _dwconv_fwd(ctx, x, w, bias, (Cc, H * W * Cc, B, H, W, 0), act)
 
     @staticmethod
     def backward(ctx, dy):
-        x, wf, z = ctx.saved_tensors
-        segs, act, has_bias, Cc = ctx.conf
-        L = _lib.lib()
-        es = x.element_size()
-        code = _code(x.dtype)
-        dy = dy.contiguous()
-        if act != ACT_NONE:
-            dz = torch.empty_like(dy)
-            _lib.check(L.du_act_bwd(code, _p(z), _p(dy), _p(dz), dy.numel(), act, _st()), "du_act_bwd")
-        else:
-            dz = dy
-        dx = torch.empty_like(x)
-        dw = torch.empty((Cc, 9), dtype=torch.float32, device=x.device)      # written by the first segment, accumulated by the rest
-        db = torch.empty(Cc, dtype=torch.float32, device=x.device) if has_bias else None
-        for si, (off, B, h, ww, ld, bs) in enumerate(segs):
-            if act == ACT_NONE and L.du_dwconv_band_ok(code, B, h, ww, Cc, 0):
-                n = int(L.du_dwconv_band_ws_elems(code, B, h, ww, Cc, 0))
-                ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
-                _lib.check(L.du_dwconv_band_bwd(code, C.c_void_p(dz.data_ptr() + off * es), C.c_void_p(x.data_ptr() + off * es), _p(wf),
-                                                C.c_void_p(dx.data_ptr() + off * es), _p(dw), _p(db), ld, bs, B, h, ww, Cc, _p(ws), n,
-                                                1 if si > 0 else 0, _st()), "du_dwconv_band_bwd")
-                continue
-            _lib.check(L.du_dwconv3x3_bwd_data(code, C.c_void_p(dz.data_ptr() + off * es), ld, bs, _p(wf),
-                                               C.c_void_p(dx.data_ptr() + off * es), ld, bs, B, h, ww, Cc, _st()),
-                       "du_dwconv3x3_bwd_data")
-            n = int(L.du_dwconv_wgrad_ws_elems(code, B, h, ww, Cc))
-            ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
-            _lib.check(L.du_dwconv3x3_bwd_weight(code, C.c_void_p(x.data_ptr() + off * es), ld, bs,
-                                                 C.c_void_p(dz.data_ptr() + off * es), ld, bs, _p(dw), _p(db), B, h, ww, Cc,
-                                                 _p(ws), n, 1 if si > 0 else 0, _st()), "du_dwconv3x3_bwd_weight")
-        return dx, dw.view(Cc, 1, 3, 3), db, None, None
+        return (*_dwconv_bwd(ctx, dy), None)
 
 
 def dwconv3x3(x, w, bias=None, act=ACT_NONE):
     """x NHWC (B,H,W,C)."""
-    x = x.contiguous()
-    B, H, W, Cc = x.shape
-    return _DWConvSegs.apply(x, w, bias, ((0, B, H, W, Cc, H * W * Cc),), act)
+    return _DWConv.apply(x, w, bias, act)
 
 
 class _DWConvTokens(torch.autograd.Function):
-    """ConvFFN's DWConv (dinov3_adapter.py:99-109) + GELU (:87) over the (B, 21 n, C) token pyramid: the three grids of every image in
-    ONE launch per pass (forward, data gradient, weight gradient) instead of one per grid."""
+    """ConvFFN's DWConv (dinov3_adapter.py:99-109) + GELU (:87) over the (B, 21 n, C) token pyramid: one depthwise kernel applied to the
+    token ranges viewed as (2H x 2W), (H x W), (H/2 x W/2) grids, the three grids of every image in ONE launch per pass."""
 
     @staticmethod
     def forward(ctx, x, w, bias, H, W, act):
-        x = x.contiguous()
         B, N, Cc = x.shape
-        wf = _f32(w).view(Cc, 9)
-        y = torch.empty_like(x)
-        z = torch.empty_like(x) if act != ACT_NONE else None
-        L = _lib.lib()
-        if L.du_dwconv_band_ok(_code(x.dtype), B, H, W, Cc, 1):      # band kernels (csrc/dwconv.hip)
-            _lib.check(L.du_dwconv_band_tokens_fwd(_code(x.dtype), _p(x), _p(wf), _p(_f32(bias)), _p(y), _p(z), B, H, W, Cc, act, _st()),
-                       "du_dwconv_band_tokens_fwd")
-        else:
-            _lib.check(L.du_dwconv3x3_tokens_fwd(_code(x.dtype), _p(x), _p(wf), _p(_f32(bias)), _p(y), _p(z), B, H, W, Cc, act, _st()),
-                       "du_dwconv3x3_tokens_fwd")
-        ctx.save_for_backward(x, wf, z)
-        ctx.conf = (H, W, act, bias is not None)
-        return y
+        return _dwconv_fwd(ctx, x, w, bias, (Cc, N * Cc, B, H, W, 1), act)
 
     @staticmethod
     def backward(ctx, dy):
-        x, wf, z = ctx.saved_tensors
-        H, W, act, has_bias = ctx.conf
-        B, N, Cc = x.shape
-        L = _lib.lib()
-        code = _code(x.dtype)
-        dy = dy.contiguous()
-        if L.du_dwconv_band_ok(code, B, H, W, Cc, 1):
-            # the data gradient applies act' on load and leaves dz for the weight gradient: no du_act_bwd pass
-            dz = torch.empty_like(dy) if act != ACT_NONE else None
-            dx = torch.empty_like(x)
-            dw = torch.empty((Cc, 9), dtype=torch.float32, device=x.device)
-            db = torch.empty(Cc, dtype=torch.float32, device=x.device) if has_bias else None
-            n = int(L.du_dwconv_band_ws_elems(code, B, H, W, Cc, 1))
-            ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
-            _lib.check(L.du_dwconv_band_tokens_bwd(code, _p(z), _p(dy), _p(x), _p(wf), _p(dx), _p(dw), _p(db), _p(dz), B, H, W, Cc, act,
-                                                   _p(ws), n, _st()), "du_dwconv_band_tokens_bwd")
-            return dx, dw.view(Cc, 1, 3, 3), db, None, None, None
-        if act != ACT_NONE:
-            dz = torch.empty_like(dy)
-            _lib.check(L.du_act_bwd(code, _p(z), _p(dy), _p(dz), dy.numel(), act, _st()), "du_act_bwd")
-        else:
-            dz = dy
-        dx = torch.empty_like(x)
-        _lib.check(L.du_dwconv3x3_tokens_bwd_data(code, _p(dz), _p(wf), _p(dx), B, H, W, Cc, _st()), "du_dwconv3x3_tokens_bwd_data")
-        dw = torch.empty((Cc, 9), dtype=torch.float32, device=x.device)
-        db = torch.empty(Cc, dtype=torch.float32, device=x.device) if has_bias else None
-        n = int(L.du_dwconv_wgrad_ws_elems(code, B, N, 1, Cc))
-        ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
-        _lib.check(L.du_dwconv3x3_tokens_bwd_weight(code, _p(x), _p(dz), _p(dw), _p(db), B, H, W, Cc, _p(ws), n, _st()),
-                   "du_dwconv3x3_tokens_bwd_weight")
-        return dx, dw.view(Cc, 1, 3, 3), db, None, None, None
+        return (*_dwconv_bwd(ctx, dy), None, None, None)
 
 
 def dwconv_tokens(x, w, bias, H, W, act=ACT_GELU):

@@ -23,9 +23,10 @@
  *   du_layernorm_fwd / _bwd      <- nn.LayerNorm (layers/block.py:43,56; dinov3_adapter.py:128-137)
  *   du_chan_stats / du_norm_act_* <- InstanceNorm2d+LeakyReLU (dinounet_training.py:401,238; decoder
  *          StackedConvBlocks :581-592) and SyncBatchNorm(+ReLU) (dinov3_adapter.py:242-270,361-364)
- *   du_dwconv3x3_* / du_dwconv_band_* <- DWConv (dinov3_adapter.py:94-109), DepthwiseSeparableConv.depthwise
- *          (dinounet_training.py:235): du_dwconv_band_* (dwconv.hip: a workgroup walks a band of rows, GELU backward
- *          fused into the data gradient) where du_dwconv_band_ok, du_dwconv3x3_* (elementwise.hip) for every other shape
+ *   du_dwconv3x3_fwd / _bwd      <- DWConv (dinov3_adapter.py:94-109), DepthwiseSeparableConv.depthwise
+ *          (dinounet_training.py:235): one call per pass; the library picks the band kernels (dwconv.hip: a workgroup walks
+ *          a band of rows, GELU backward fused into the data gradient) or the row kernels (elementwise.hip) by the plan
+ *          of csrc/dwconv_plan.h; du_dwconv3x3_plan_describe reports that plan
  *   du_maxpool3x3s2_*            <- nn.MaxPool2d(3,2,1) (dinov3_adapter.py:250)
  *   du_bilinear_add_*            <- F.interpolate(bilinear, align_corners=False)+add (dinov3_adapter.py:472-476)
  *   du_se_gate_* / du_se_scale_*  <- SqueezeExcitation + residual (dinounet_training.py:210-225,438)
@@ -379,45 +380,30 @@ int du_msda_prep_bwd(int dtype, const float* attn, const float* gloc, const floa
                      int64_t rows, int M, int P, int Hs, int Ws, void* stream);
 
 /* ---- small conv-side ops (NHWC; `*bs` = per-image stride in elements so token ranges can be viewed as images) ---- */
-/* y = act(dwconv3x3(x) + bias); z (nullable) receives the pre-activation. w: (C,3,3) fp32. */
-int du_dwconv3x3_fwd(int dtype, const void* x, int64_t ldx, int64_t xbs, const float* w, const float* bias, void* y,
-                     int64_t ldy, int64_t ybs, void* z, int B, int H, int W, int C, int act, void* stream);
-int du_dwconv3x3_bwd_data(int dtype, const void* dy, int64_t lddy, int64_t dybs, const float* w, void* dx, int64_t lddx,
-                          int64_t dxbs, int B, int H, int W, int C, void* stream);
-/* dw (C,9) and db (C, nullable).  With scratch `ws` (>= du_dwconv_wgrad_ws_elems floats) the result is written (accumulate = 0)
-   or added to dw/db (accumulate = 1: further image segments of the same kernel); with ws == NULL partials are added with atomics
-   into buffers the caller zero-filled. */
-int64_t du_dwconv_wgrad_ws_elems(int dtype, int B, int H, int W, int C);
-int du_dwconv3x3_bwd_weight(int dtype, const void* x, int64_t ldx, int64_t xbs, const void* dy, int64_t lddy, int64_t dybs,
-                            float* dw, float* db, int B, int H, int W, int C, float* ws, int64_t ws_elems, int accumulate,
-                            void* stream);
-/* The same depthwise kernel over ConvFFN's token pyramid (DWConv.forward, dinov3_adapter.py:99-109): x, y, z, dy, dx are contiguous
-   (B, 21 n, C) token tensors, n = H*W/4, each image holding a (2H x 2W), an (H x W) and an (H/2 x W/2) grid back to back; one launch
-   instead of one per grid.  z (nullable): pre-activation copy for the backward of `act`.  bwd_weight OVERWRITES dw (C,9) / db (C) and
-   needs du_dwconv_wgrad_ws_elems(dtype, B, 21 n, 1, C) floats of scratch. */
-int du_dwconv3x3_tokens_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, void* z, int B, int H, int W, int C,
-                            int act, void* stream);
-int du_dwconv3x3_tokens_bwd_data(int dtype, const void* dy, const float* w, void* dx, int B, int H, int W, int C, void* stream);
-int du_dwconv3x3_tokens_bwd_weight(int dtype, const void* x, const void* dy, float* dw, float* db, int B, int H, int W, int C, float* ws,
-                                   int64_t ws_elems, void* stream);
-/* Band-tiled forms of the kernels above (csrc/dwconv.hip): bf16, C % 8 == 0, every grid width even.  du_dwconv_band_ok returns 1 exactly
-   when they will run for (B, H, W, C) -- pyramid != 0: the token pyramid of du_dwconv3x3_tokens_* (H, W as there), else one NHWC segment --
-   and 0 otherwise (fp32, odd widths, C % 8, du_set_option(19, 0)): the caller then uses du_dwconv3x3_*.  y, z and dx have the bits of the
-   kernels above; dw / db are the same fp32 sums in another order.
-   _tokens_bwd: z (pre-activation) and dz (scratch, same shape as dy) are needed when act != DU_ACT_NONE and may be NULL otherwise: the
-   data gradient forms dz = bf16(dy * act'(z)) on load (no du_act_bwd pass), writes dx and leaves dz for the weight gradient.  It OVERWRITES
-   dx, dw (C,9) and db (C, nullable).  _bwd (one NHWC segment, no activation; x, dy, dx share ld / bs): accumulate = 1 adds to dw / db.
-   ws: du_dwconv_band_ws_elems floats (one partial row per workgroup, summed by one small second launch). */
-int du_dwconv_band_ok(int dtype, int B, int H, int W, int C, int pyramid);
-int64_t du_dwconv_band_ws_elems(int dtype, int B, int H, int W, int C, int pyramid);
-int du_dwconv_band_tokens_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, void* z, int B, int H, int W, int C,
-                              int act, void* stream);
-int du_dwconv_band_tokens_bwd(int dtype, const void* z, const void* dy, const void* x, const float* w, void* dx, float* dw, float* db,
-                              void* dz, int B, int H, int W, int C, int act, float* ws, int64_t ws_elems, void* stream);
-int du_dwconv_band_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, int64_t ld, int64_t bs, int B, int H, int W,
-                       int C, void* stream);
-int du_dwconv_band_bwd(int dtype, const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, int64_t ld, int64_t bs,
-                       int B, int H, int W, int C, float* ws, int64_t ws_elems, int accumulate, void* stream);
+/* Depthwise 3x3 (stride 1, pad 1), y = act(dwconv3x3(x) + bias); w: (C,3,3) fp32, bias (C, nullable) fp32.
+   pyramid == 0: one NHWC segment, B images of H x W pixels; `ld` = pixel stride and `bs` = image stride in elements, shared by EVERY
+   tensor of the call (x, y, z, dy, dx, dz: a call serves tensors laid out alike).
+   pyramid != 0: ConvFFN's token pyramid (DWConv.forward, dinov3_adapter.py:99-109): contiguous (B, 21 n, C) token tensors, n = H*W/4, each
+   image holding a (2H x 2W), an (H x W) and an (H/2 x W/2) grid back to back, one launch per pass; ld == C and bs == 21 n C.
+   The library picks the kernel (csrc/dwconv_plan.h: du_dwconv_plan decides once per call, the entries below execute or read it): the
+   band kernels of dwconv.hip for bf16, C % 8 == 0, even grid widths, ld % 8 == 0, bs % 8 == 0 -- the pyramid with any activation, an
+   NHWC segment with DU_ACT_NONE -- and the row kernels of elementwise.hip otherwise (C, ld, bs multiples of 8 bf16 / 4 fp32; H, W even
+   for the pyramid).  y, z and dx have the same bits on either family; dw / db are the same fp32 sums in another order.
+   _fwd: z (nullable) receives the pre-activation, which the backward of `act` needs.
+   _bwd: ONE call per backward; it OVERWRITES dx, dw (C,9) and db (C, nullable) and needs du_dwconv3x3_bwd_ws_elems floats of scratch
+   (partial rows, summed by a small second launch; fewer is DU_ERR_BAD_ARG before anything launches).  z (pre-activation) and dz (scratch,
+   shaped as dy) are required exactly when act != DU_ACT_NONE: dz = dy * act'(z) is formed on load by the band data gradient, by a launch
+   of du_act_bwd's kernel in the row family -- which needs dense tensors (ld == C, bs == H*W*C) there: DU_ERR_UNSUPPORTED otherwise.
+   _plan_describe: out[0..6] = {rc the call would return before launching, forward / data-gradient kernel (1 dwconv_kernel, 2
+   dwconv_row4_kernel, 3 dwconv_band_kernel), its band height (0: row kernels), activation backward (0 none, 1 a separate act_bwd_kernel
+   launch, 2 on load in dwconv_band_dgrad_act_kernel), weight-gradient kernel (1 dwconv_bwd_weight_kernel<T, false>, 2 <T, true>,
+   3 <bf16, true, true>, 4 dwconv_band_wgrad_kernel), its partial rows, scratch floats}; returns 7, DU_ERR_BAD_ARG for out == NULL or n < 7. */
+int du_dwconv3x3_fwd(int dtype, const void* x, const float* w, const float* bias, void* y, void* z, int64_t ld, int64_t bs, int B, int H,
+                     int W, int C, int pyramid, int act, void* stream);
+int64_t du_dwconv3x3_bwd_ws_elems(int dtype, int64_t ld, int64_t bs, int B, int H, int W, int C, int pyramid, int act);
+int du_dwconv3x3_bwd(int dtype, const void* z, const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, void* dz,
+                     int64_t ld, int64_t bs, int B, int H, int W, int C, int pyramid, int act, float* ws, int64_t ws_elems, void* stream);
+int du_dwconv3x3_plan_describe(int dtype, int64_t ld, int64_t bs, int B, int H, int W, int C, int pyramid, int act, int64_t* out, int n);
 /* MaxPool2d(3, 2, 1) on contiguous NHWC; idx (nullable, same shape as y, uint8) records the winning tap */
 int du_maxpool3x3s2_fwd(int dtype, const void* x, void* y, uint8_t* idx, int B, int H, int W, int C, void* stream);
 int du_maxpool3x3s2_bwd(int dtype, const uint8_t* idx, const void* dy, void* dx, int B, int H, int W, int C, void* stream);
@@ -595,8 +581,8 @@ int du_device_ok(void); /* 1 if the current device is gfx950 */
            meet through du_gemm_args.ks_ws: 1 (default), 0 = one unit per 32 columns walks the whole contraction;
    key 18: du_layernorm_fwd with two rows per wave: 1 = where the rows overflow one round of waves (32 per CU) by less than 2x -- the ViT's
            8232 rows (default), 0 = never, 2 = always;
-   key 19: depthwise 3 x 3 on the band kernels (dwconv.hip) where du_dwconv_band_ok: 1 (default), 0 = the kernels of elementwise.hip
-           everywhere (du_dwconv_band_ok then returns 0); tuning aid: bits 0-7 >= 2 = bands of that many rows in forward and data
+   key 19: depthwise 3 x 3 on the band kernels (dwconv.hip) where the plan of du_dwconv3x3_* allows: 1 (default), 0 = the kernels of
+           elementwise.hip everywhere (du_dwconv3x3_plan_describe then names a row kernel); tuning aid: bits 0-7 >= 2 = bands of that many rows in forward and data
            gradient, bits 8-15 >= 2 = in the weight gradient, instead of the height the library picks;
    key 14: bf16 products with a bf16 residual on the persistent kernel (the residual as two more K-steps): 1 (default), 0 = one-shot kernels;
    key 9: number of independent products the caller keeps in flight on DIFFERENT streams (default 1; dinounet_amd runs the frozen ViT as

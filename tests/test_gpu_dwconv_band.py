@@ -39,9 +39,26 @@ class option:
         return False
 
 
-def band_ok(B, H, W, Cc, pyramid):
+ROW, ROW4, BAND = 1, 2, 3                    # du_dwconv3x3_plan_describe, out[1]
+
+
+def describe(dtype, B, H, W, Cc, pyramid, act, ld=None):
+    """du_dwconv3x3_plan_describe of a call on dense tensors (or an NHWC tensor of pixel stride ld)"""
+    import ctypes
     from dinounet_amd import _lib, ops
-    return int(_lib.lib().du_dwconv_band_ok(ops._code(bf), B, H, W, Cc, pyramid))
+    ld = ld or Cc
+    pix = 21 * (H * W // 4) if pyramid else H * W
+    d = (ctypes.c_int64 * 7)()
+    assert _lib.lib().du_dwconv3x3_plan_describe(ops._code(dtype), ld, pix * ld, B, H, W, Cc, pyramid, act, d, 7) == 7
+    return list(d)
+
+
+def band_ok(B, H, W, Cc, pyramid, dtype=bf):
+    """1: the band family serves the call as this file makes it (the pyramid with GELU or without, one NHWC segment without activation)"""
+    from dinounet_amd._lib import ACT_GELU, ACT_NONE
+    ds = [describe(dtype, B, H, W, Cc, pyramid, act) for act in ((ACT_GELU, ACT_NONE) if pyramid else (ACT_NONE,))]
+    assert len({(d[0], d[1] == BAND) for d in ds}) == 1, ds
+    return int(ds[0][0] == 0 and ds[0][1] == BAND)
 
 
 def grids(H, W):
@@ -93,14 +110,15 @@ def run(x, w, b, go, pyramid, H, W, act):
 
 
 def forward_z(x, w, b, H, W, act, band):
-    """the pre-activation copy of the pyramid forward, straight from the entry points (autograd keeps it to itself)"""
+    """the pre-activation copy of the pyramid forward, straight from the entry point (autograd keeps it to itself), under option(band):
+    0 = the row kernels, 1 = the band kernels, >= 2 = bands of that many rows; the option is back at its default afterwards"""
     from dinounet_amd import _lib, ops
-    L = _lib.lib()
     B, N, Cc = x.shape
     y, z = torch.empty_like(x), torch.empty_like(x)
-    fn = L.du_dwconv_band_tokens_fwd if band else L.du_dwconv3x3_tokens_fwd
-    _lib.check(fn(ops._code(x.dtype), ops._p(x), ops._p(w.float().view(Cc, 9).contiguous()), ops._p(b.float()), ops._p(y), ops._p(z), B, H, W, Cc,
-                  act, ops._st()), "dwconv tokens forward")
+    with option(int(band)):
+        assert band_ok(B, H, W, Cc, 1) == int(band != 0)
+        _lib.check(_lib.lib().du_dwconv3x3_fwd(ops._code(x.dtype), ops._p(x), ops._p(w.float().view(Cc, 9).contiguous()), ops._p(b.float()), ops._p(y),
+                                               ops._p(z), Cc, N * Cc, B, H, W, Cc, 1, act, ops._st()), "du_dwconv3x3_fwd")
     return y, z
 
 
@@ -129,12 +147,12 @@ def test_band_equals_old_kernels_bitwise(pyramid, cfg):
         with option(0):
             assert band_ok(B, H, W, Cc, pyramid) == 0
             y0, dx0, dw0, db0 = run(x, w, b, go, pyramid, H, W, act)
-            z0 = forward_z(x, w, b, H, W, act, band=False)[1] if pyramid else None
+        z0 = forward_z(x, w, b, H, W, act, band=False)[1] if pyramid else None
         for rows in (1, 8):                     # the library's band height (4 rows at these sizes), and bands of 8 rows
             with option(rows):
                 assert band_ok(B, H, W, Cc, pyramid) == 1
                 y1, dx1, dw1, db1 = run(x, w, b, go, pyramid, H, W, act)
-                yb, z1 = forward_z(x, w, b, H, W, act, band=True) if pyramid else (y1, None)
+            yb, z1 = forward_z(x, w, b, H, W, act, band=rows) if pyramid else (y1, None)
             assert torch.equal(y0, y1), f"y differs (act {act}): {X.mismatch_report(y1.flatten(0, -2).cpu(), y0.flatten(0, -2).cpu())}"
             assert torch.equal(dx0, dx1), f"dx differs (act {act}): {X.mismatch_report(dx1.flatten(0, -2).cpu(), dx0.flatten(0, -2).cpu())}"
             if pyramid:
@@ -214,12 +232,11 @@ def test_band_autograd(pyramid, cfg):
 
 def test_band_declined_shapes():
     """(e) W = 6 (a 3-wide grid in the pyramid), an odd NHWC width, fp32: the query says 0 and the result is the old kernels'"""
-    from dinounet_amd import _lib, ops
     from dinounet_amd._lib import ACT_GELU, ACT_NONE
     B, H, W, Cc = 2, 8, 6, 64
     assert band_ok(B, H, W, Cc, 1) == 0 and band_ok(2, 9, 7, 32, 0) == 0
-    assert int(_lib.lib().du_dwconv_band_ok(ops._code(torch.float32), 3, 8, 8, 64, 1)) == 0
-    assert int(_lib.lib().du_dwconv_band_ok(ops._code(bf), 3, 8, 8, 60, 1)) == 0
+    assert band_ok(3, 8, 8, 64, 1, dtype=torch.float32) == 0
+    assert band_ok(3, 8, 8, 60, 1) == 0
     x, w, b, go = inputs(B, H, W, Cc, 1, seed=50)
     res = run(x, w, b, go, 1, H, W, ACT_GELU)
     with option(0):
@@ -234,3 +251,67 @@ def test_band_declined_shapes():
         assert torch.equal(a, o)
     yr, dxr, dwr, dbr = ref64(x, w, b, go, 0, 9, 7)
     assert rel(res[0], yr) < TOL[bf] and rel64(res[2], dwr.to(dev())) < 2e-5
+
+
+@pytest.mark.parametrize("cfg", NHWC, ids=["-".join(map(str, c)) for c in NHWC])
+def test_nhwc_with_gelu_stays_on_the_row_kernels(cfg):
+    """(f) the one combination the band family declines for a band-shaped tensor: the plan says row kernels with a separate activation
+    pass under either option, y and dx have the same bits under both, and the result is F.conv2d + F.gelu's"""
+    from dinounet_amd._lib import ACT_GELU
+    B, H, W, Cc = cfg
+    assert band_ok(B, H, W, Cc, 0) == 1
+    x, w, b, go = inputs(B, H, W, Cc, 0, seed=60)
+    res = []
+    for opt in (0, 1):
+        with option(opt):
+            assert describe(bf, B, H, W, Cc, 0, ACT_GELU)[:5] == [0, ROW, 0, 1, 1]
+            res.append(run(x, w, b, go, 0, H, W, ACT_GELU))
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+    xr = x.float().cpu().requires_grad_(True)
+    wr, br = w.cpu().clone().requires_grad_(True), b.cpu().clone().requires_grad_(True)
+    yr = F.gelu(F.conv2d(xr.permute(0, 3, 1, 2), wr, br, 1, 1, groups=Cc).permute(0, 2, 3, 1))
+    gr = torch.autograd.grad(yr, (xr, wr, br), go.float().cpu())
+    y, dx, dw, db = res[1]
+    assert rel(y, yr) < TOL[bf]
+    for a, r_ in zip((dx, dw, db), gr):
+        assert rel(a, r_) < TOL[bf]
+
+
+# (dtype, B, H, W, C, pyramid, act, ld or None) -> what describe must say: {rc, forward kernel}
+DECLINED = [
+    ((bf, 2, 8, 6, 64, 1, 1, None), [0, ROW]),                   # a 3-wide grid in the pyramid
+    ((bf, 2, 9, 7, 32, 0, 0, None), [0, ROW]),                   # an odd NHWC width
+    ((torch.float32, 3, 8, 8, 64, 1, 1, None), [0, ROW]),        # fp32 (W % 8 == 0: the 4-pixel kernel is bf16 only)
+    ((bf, 3, 8, 8, 60, 1, 1, None), [-1, 0]),                    # C % 8: neither family
+    ((bf, 2, 12, 20, 32, 0, 0, 36), [-1, ROW]),                  # band-shaped, but pixels 72 bytes apart: the row family's DU_ERR_BAD_ARG
+]
+
+
+@pytest.mark.parametrize("call,want", DECLINED, ids=[f"{'pyr' if c[5] else 'nhwc'}-{'-'.join(map(str, c[1:5]))}-{str(c[0])[6:]}-ld{c[7]}" for c, _ in DECLINED])
+def test_declined_calls_return_what_describe_says(call, want):
+    """(g) describe reports the row family's decision, or its DU_ERR_BAD_ARG, and du_dwconv3x3_fwd / _bwd return that code; a refused call
+    writes nothing"""
+    from dinounet_amd import _lib, ops
+    dt, B, H, W, Cc, pyramid, act, ld = call
+    L, d = _lib.lib(), dev()
+    desc = describe(dt, B, H, W, Cc, pyramid, act, ld)
+    assert desc[:2] == want
+    ld = ld or Cc
+    pix = 21 * (H * W // 4) if pyramid else H * W
+    bs = pix * ld
+    x, go = gen(B, pix, ld, seed=70).to(d, dt), gen(B, pix, ld, seed=71).to(d, dt)
+    w, b = gen(Cc, 9, seed=72, scale=1 / 3).to(d), gen(Cc, seed=73).to(d)
+    y, z, dx, dz = (torch.full_like(x, 7.0) for _ in range(4))
+    dw, db = torch.full((Cc, 9), 7.0, device=d), torch.full((Cc,), 7.0, device=d)
+    geom = (ld, bs, B, H, W, Cc, pyramid, act)
+    assert L.du_dwconv3x3_fwd(ops._code(dt), ops._p(x), ops._p(w), ops._p(b), ops._p(y), ops._p(z), *geom, ops._st()) == want[0]
+    n = int(L.du_dwconv3x3_bwd_ws_elems(ops._code(dt), *geom))
+    assert n == desc[6]
+    ws = torch.empty(max(n, 1), dtype=torch.float32, device=d)
+    assert L.du_dwconv3x3_bwd(ops._code(dt), ops._p(z), ops._p(go), ops._p(x), ops._p(w), ops._p(dx), ops._p(dw), ops._p(db), ops._p(dz), *geom,
+                              ops._p(ws), n, ops._st()) == want[0]
+    torch.cuda.synchronize()
+    if want[0] != 0:
+        assert all(bool((t == 7.0).all()) for t in (y, z, dx, dz, dw, db))
+    else:
+        assert not bool((y == 7.0).all()) and not bool((dx == 7.0).all()) and not bool((dw == 7.0).any())
