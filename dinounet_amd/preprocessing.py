@@ -35,7 +35,8 @@ Differences from the reference, on purpose:
   * ZScoreNormalization takes mean and standard deviation in fp64 (two passes) and rounds the result once; numpy's float32 recipe differs
     from that by its own summation error (DESIGN 3e has the figure);
   * the image comes out of the crop as fp32 whatever its dtype was;
-  * properties['class_locations'] (:94-111) is training-set preparation with a host RNG and is not produced."""
+  * properties['class_locations'] (:94-111) is training-set preparation with a host RNG: run_case leaves it out,
+    dataloading.add_class_locations fills it from the returned segmentation."""
 import math
 
 import numpy as np
@@ -477,7 +478,8 @@ def run_case(data, seg, properties, *, transpose_forward, spacing, normalization
     configuration's `spacing` (two entries for a 2-D configuration: the case's own slice spacing is prepended, :69-72).  Fills
     properties['shape_before_cropping'], ['bbox_used_for_cropping'] and ['shape_after_cropping_and_before_resampling'], which
     export.predict_segmentation reads.  Returns (data fp32 (C, D, H', W'), seg int16 (1, D, H', W')) on the input's device; the inputs
-    are not modified.  properties['class_locations'] (:94-111: foreground sampling for training, a host RNG) is not produced."""
+    are not modified.  properties['class_locations'] (:94-111: foreground sampling for training, a host RNG) is filled by
+    dataloading.add_class_locations(seg, properties, ...), not here."""
     tf = _check_transpose(transpose_forward)
     if not isinstance(data, torch.Tensor) or data.ndim != 4:
         raise ValueError("data must be a (C, X, Y, Z) torch tensor")

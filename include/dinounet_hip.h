@@ -744,6 +744,33 @@ int du_pre_normalize(float* img, const int16_t* seg, const double* chan_stats, i
 int du_pre_resize_cubic(const float* in, float* out, const float* bounds, double* tmp, int P, int H, int W, int Ho, int Wo, void* stream);
 int du_pre_resize_seg(const int16_t* in, int16_t* out, int D, int H, int W, int Ho, int Wo, void* stream);
 
+/* ---- training batches (csrc/dataload.hip): the class-location tables of DefaultPreprocessor._sample_foreground_locations
+   (dinounet/preprocessing/preprocessors/default_preprocessor.py:157-181) and the batch gather of nnUNetDataLoader2D.generate_train_batch
+   (dinounet/training/dataloading/data_loader_2d.py:46-85).  Every launch goes on `stream`; no call reads anything back.
+   seg (D, H, W) int16, read-only, D H W < 2^31.  masks (G) int64 DEVICE: a voxel is a member of mask g if 0 <= label <= 63 and bit `label`
+   of masks[g] is set (the du_labels_to_regions convention; any other label is in no mask).  Members are ranked in the raster order
+   (z H + y) W + x, the order np.argwhere lists them in.
+   du_dl_class_counts: ws (G, nchunks) int32 = per mask the exclusive prefix of the member counts of the chunks of 1024 consecutive voxels,
+   nchunks = ceil(D H W / 1024); totals (G) int64 DEVICE = the member count of every mask.  Two kernels, no atomics.
+   du_dl_select: ws as du_dl_class_counts left it for the same seg, masks and G; ranks (m) int64 DEVICE in any order, each in
+   [0, totals[g]); out (m, 4) int32 = {0, z, y, x} of the member of mask g with that rank, i.e. np.argwhere(mask)[ranks] of the mask seen as
+   (1, D, H, W).  A rank outside [0, totals[g]) gives {0, -1, -1, -1}.  One wave per rank: a binary search over the prefix, then ballots and
+   popcounts over one chunk.
+   ws: du_dl_ws_elems(D, H, W, G) int32 elements = G nchunks rounded up to 4, 16-byte aligned.
+   DU_ERR_UNSUPPORTED: D H W >= 2^31.  DU_ERR_BAD_ARG: a NULL or misaligned pointer, an extent, G or m < 1, g outside [0, G), m > D H W, ws
+   misaligned or ws_elems below du_dl_ws_elems.  du_dl_ws_elems launches nothing and returns that (negative) code itself for such a shape.
+   du_dl_gather: one launch for a batch.  jobs (B, 8) int64 DEVICE, row b = {address of data (C, D, H, W) fp32, address of seg (D, H, W) int16,
+   D, H, W, slice, y0, x0}; the cases may differ in D, H, W, not in C; y0 / x0 may be negative or run past the image.
+   data_out (B, C, ph, pw) fp32 = data[:, slice, y0 : y0 + ph, x0 : x0 + pw], 0 outside the image; seg_out (B, 1, ph, pw) = the same window of
+   seg, -1 outside: int16, or fp32 with seg_f32 != 0 (what du_aug_spatial takes).  A row whose slice is outside [0, D) reads as outside
+   everywhere.  The inputs are not modified.  DU_ERR_BAD_ARG: NULL or misaligned pointer, B, C, ph or pw < 1. ---- */
+int64_t du_dl_ws_elems(int D, int H, int W, int G);
+int du_dl_class_counts(const int16_t* seg, const int64_t* masks, int G, int D, int H, int W, int32_t* ws, int64_t ws_elems, int64_t* totals,
+                       void* stream);
+int du_dl_select(const int16_t* seg, const int64_t* masks, int G, int g, int D, int H, int W, const int32_t* ws, int64_t ws_elems,
+                 const int64_t* ranks, int64_t m, int32_t* out, void* stream);
+int du_dl_gather(const int64_t* jobs, int B, int C, int ph, int pw, float* data_out, void* seg_out, int seg_f32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
