@@ -771,6 +771,36 @@ int du_dl_select(const int16_t* seg, const int64_t* masks, int G, int g, int D, 
                  const int64_t* ranks, int64_t m, int32_t* out, void* stream);
 int du_dl_gather(const int64_t* jobs, int B, int C, int ph, int pw, float* data_out, void* seg_out, int seg_f32, void* stream);
 
+/* ---- dataset fingerprint (csrc/fingerprint.hip): the foreground statistics and samples of DatasetFingerprintExtractor
+   (dinounet/experiment_planning/dataset_fingerprint/fingerprint_extractor.py:42-80 per case, :156-177 over the dataset).  Every launch goes
+   on `stream`; no call reads anything back.
+   img (C, n) fp32 and seg (n) int16 or NULL, read-only, n < 2^31, C <= 65535.  An element is a member if seg > 0; with NULL every element
+   is (the dataset-level form over the concatenated samples).  Every channel has the same members.
+   du_fp_moments: stats (C, 6) fp64 DEVICE = {member count, min, max, sum, count of NaN members, -}.  mode 0 writes the first five and
+   zeroes the sixth: the sum in fp64 in a fixed order (per lane in sequence, lanes by the xor tree, waves and stretches in order), min and
+   max over the members that are not NaN, +inf and -inf without members.  mode 1 reads count and sum and writes stats[c][5] = the fp64 sum
+   of (x - sum / count)^2 over the members, the second pass.  Two kernels each, no atomics.
+   du_fp_order_stats: ranks (C, R) int64 DEVICE, 1 <= R <= 8, each in [0, count); out (C, R) fp32 = the member of channel c whose 0-based
+   position in ascending order is ranks[c][r], i.e. np.sort(members)[rank], -0.0 sorted below +0.0.  Radix select over the order-preserving
+   32-bit key, 8 bits a pass: four sweeps over img and seg, each followed by a one-workgroup kernel per channel; all C R targets are
+   served by the same sweeps.  Integer atomics only.  The ranks live on the device, so the call cannot refuse one: a rank outside
+   [0, count) gives NaN in its place and disturbs no other target.
+   du_fp_sample: ranks (C, m) int64 DEVICE in the raster order of the members, in any order, repeats allowed; out (C, m) fp32 =
+   img[c][members[ranks[c][j]]], i.e. images[c][mask][ranks[c]].  With seg: member counts of the chunks of 1024 elements, their exclusive
+   prefix, then one wave per rank (du_dl_select's scheme with the predicate seg > 0); without: a plain gather.  A rank outside [0, count)
+   gives NaN.
+   ws of all three: du_fp_ws_elems(C, n) int32 elements, 16-byte aligned; the calls of one stream may share it, nothing is kept in it
+   between calls.  DU_ERR_UNSUPPORTED: n >= 2^31, C > 65535, or m >= 2^40 (du_fp_sample).  DU_ERR_BAD_ARG: a NULL (seg excepted) or misaligned pointer, C, n or m < 1,
+   R outside 1..8, mode outside {0, 1}, ws_elems below du_fp_ws_elems.  du_fp_ws_elems launches nothing and returns that (negative) code
+   itself for such a shape. ---- */
+int64_t du_fp_ws_elems(int C, int64_t n);
+int du_fp_moments(const float* img, const int16_t* seg, int C, int64_t n, int mode, double* stats, int32_t* ws, int64_t ws_elems,
+                  void* stream);
+int du_fp_order_stats(const float* img, const int16_t* seg, int C, int64_t n, const int64_t* ranks, int R, float* out, int32_t* ws,
+                      int64_t ws_elems, void* stream);
+int du_fp_sample(const float* img, const int16_t* seg, int C, int64_t n, const int64_t* ranks, int64_t m, float* out, int32_t* ws,
+                 int64_t ws_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
