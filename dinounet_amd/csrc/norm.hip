@@ -1,6 +1,7 @@
 // LayerNorm (token rows) and channel-statistics norms (InstanceNorm2d / BatchNorm2d on NHWC) for gfx950.
 // All are HBM-bound: 16-byte vector loads, fp32 statistics, wave64 shuffle reductions, one pass per tensor.
 #include "common.h"
+#include "ln_bwd_row.h"
 
 int g_ln_rows2 = 1;      // du_set_option key 18: LayerNorm forward with two rows per wave: 0 never, 1 where one round of waves overflows by < 2x (default), 2 always
 
@@ -220,25 +221,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_fused_kernel(const T* __res
     for (int u = 0; u < 2; u++) {
       const long row = row0 + 4 * u;
       if (row >= r1) break;
+      // (the fp32 operations themselves are ln_bwd_row.h's: layernorm_bwd_prod_kernel of norm_gemm.hip computes the same bits)
       float xh[MAXV][VI], g[MAXV][VI];
       float c1 = 0.f, c2 = 0.f;
 #pragma unroll
       for (int i = 0; i < MAXV; i++) {
         const int vi = lane + i * 64;
-        if (vi < nvec) {
-          Vec16<T> tx = as_vec<T>(rx[u][i]);
-          Vec16<T> tg = as_vec<T>(rg[u][i]);
-#pragma unroll
-          for (int j = 0; j < VI; j++) {
-            const float gy = to_f32(tg.v[j]);
-            xh[i][j] = (to_f32(tx.v[j]) - mu[u]) * rs[u];
-            g[i][j] = gy * wv[i][j];
-            c1 += g[i][j];
-            c2 += g[i][j] * xh[i][j];
-            sa[i][j] += gy * xh[i][j];
-            sb[i][j] += gy;
-          }
-        }
+        if (vi < nvec) ln_bwd_row_terms<T>(rx[u][i], rg[u][i], mu[u], rs[u], wv[i], xh[i], g[i], c1, c2, sa[i], sb[i]);
       }
       c1 = wave_sum(c1) / (float)D;
       c2 = wave_sum(c2) / (float)D;
@@ -246,16 +235,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_fused_kernel(const T* __res
       for (int i = 0; i < MAXV; i++) {
         const int vi = lane + i * 64;
         if (vi < nvec) {
-          Vec16<T> o;
-          if (dres) {
-            Vec16<T> tr = as_vec<T>(*(const uint4*)(dres + row * (long)D + (long)vi * VI));
-#pragma unroll
-            for (int j = 0; j < VI; j++) o.v[j] = from_f32<T>(rs[u] * (g[i][j] - c1 - xh[i][j] * c2) + to_f32(tr.v[j]));
-          } else {
-#pragma unroll
-            for (int j = 0; j < VI; j++) o.v[j] = from_f32<T>(rs[u] * (g[i][j] - c1 - xh[i][j] * c2));
-          }
-          *(uint4*)(dx + row * (long)D + (long)vi * VI) = as_u4(o);
+          uint4 o;
+          if (dres) o = ln_bwd_row_dx<T, true>(xh[i], g[i], c1, c2, rs[u], *(const uint4*)(dres + row * (long)D + (long)vi * VI));
+          else o = ln_bwd_row_dx<T, false>(xh[i], g[i], c1, c2, rs[u], make_uint4(0, 0, 0, 0));
+          *(uint4*)(dx + row * (long)D + (long)vi * VI) = o;
         }
       }
     }
@@ -855,6 +838,13 @@ int ln_bwd_dispatch(const void* x, const void* dy, const float* w, const float* 
 }
 
 }  // namespace
+
+// norm_gemm.hip: `strips` partial rows part[strip][C][2] -> PLANAR out (all first components, then all second), as strip_launch with scratch
+int du_norm_finalize_planar(const float* part, float* out, int strips, int C, hipStream_t st) {
+  if ((long)C * 2 >= 4096) hipLaunchKernelGGL(finalize_kernel<32>, dim3((unsigned)((C * 2 + 31) / 32)), dim3(256), 0, st, part, out, 1, strips, C * 2, 2);
+  else hipLaunchKernelGGL(finalize_kernel<4>, dim3((unsigned)((C * 2 + 3) / 4)), dim3(256), 0, st, part, out, 1, strips, C * 2, 2);
+  return du_check_launch();
+}
 
 extern "C" int du_layernorm_fwd(int in_dtype, int out_dtype, const void* x, int64_t ldx, const float* w, const float* b, void* y,
                                 int64_t ldy, float* mean_out, float* rstd_out, int64_t rows, int D, float eps, void* stream) {

@@ -57,9 +57,11 @@ class MSDeformAttn(nn.Module):
         nn.init.constant_(self.output_proj.bias.data, 0.0)
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
-                input_padding_mask=None, residual=None):
+                input_padding_mask=None, residual=None, query_norm=None):
         """query (N, Lq, C), reference_points (Lq, 2) [(x, y), shared by the batch], input_flatten (N, S, C),
-        input_spatial_shapes [(H, W)] python list (single level).  Returns output_proj(msda) (+ residual)."""
+        input_spatial_shapes [(H, W)] python list (single level).  Returns output_proj(msda) (+ residual).
+        query_norm (a LayerNorm module): `query` arrives un-normalised; the norm runs here, in one autograd node with the offsets | weights
+        product that is its only consumer (ops.layer_norm_offsets_prep), and the un-normalised query is the residual."""
         assert input_padding_mask is None and self.n_levels == 1 and len(input_spatial_shapes) == 1
         N, Lq, _ = query.shape
         _, S, _ = input_flatten.shape
@@ -69,8 +71,14 @@ class MSDeformAttn(nn.Module):
         value = ops.linear(input_flatten, self.value_proj.weight, self.value_proj.bias)
         value = value.view(N, S, M, value.shape[-1] // M)
         # MSA:188-197: offsets | weights product (fp32, MSA:30) + reference-point / softmax step as one autograd node (ops._OffsetsPrep)
-        loc, attn = ops.offsets_prep(query, self.sampling_offsets.weight, self.attention_weights.weight, self.sampling_offsets.bias,
-                                     self.attention_weights.bias, reference_points, Lq, M, P, Hs, Ws)
+        if query_norm is not None:
+            loc, attn, residual = ops.layer_norm_offsets_prep(query, query_norm.weight, query_norm.bias, query_norm.eps,
+                                                              self.sampling_offsets.weight, self.attention_weights.weight,
+                                                              self.sampling_offsets.bias, self.attention_weights.bias, reference_points,
+                                                              Lq, M, P, Hs, Ws)
+        else:
+            loc, attn = ops.offsets_prep(query, self.sampling_offsets.weight, self.attention_weights.weight, self.sampling_offsets.bias,
+                                         self.attention_weights.bias, reference_points, Lq, M, P, Hs, Ws)
         shapes, lsi = _level_tensors(Hs, Ws, query.device)   # cached: no host->device copy (sync) per call
         out = ops.msda(value, shapes, lsi, loc.view(N, Lq, M, 1, P, 2), attn.view(N, Lq, M, 1, P))   # MSA:207-214
         return ops.linear(out, self.output_proj.weight, self.output_proj.bias, residual=residual)
@@ -106,8 +114,13 @@ class ConvFFN(nn.Module):
         self.fc2 = nn.Linear(hidden_features, out_features)
         self.drop = nn.Dropout(drop)
 
-    def forward(self, x, H, W, residual=None, row_scale=None):
-        h = ops.linear(x, self.fc1.weight, self.fc1.bias)
+    def forward(self, x, H, W, residual=None, row_scale=None, norm=None):
+        """norm (a LayerNorm module): `x` arrives un-normalised; the norm runs in one autograd node with fc1, its only consumer
+        (ops.layer_norm_linear), and the un-normalised x is the residual."""
+        if norm is not None:
+            h, residual = ops.layer_norm_linear(x, norm.weight, norm.bias, norm.eps, self.fc1.weight, self.fc1.bias)
+        else:
+            h = ops.linear(x, self.fc1.weight, self.fc1.bias)
         h = ops.dwconv_tokens(h, self.dwconv.dwconv.weight, self.dwconv.dwconv.bias, H, W, ACT_GELU)   # ADP:99-109 + :87
         return ops.linear(h, self.fc2.weight, self.fc2.bias, residual=residual, row_scale=row_scale, rs_rows=x.shape[1])
 
@@ -152,13 +165,13 @@ class Extractor(nn.Module):
             self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
 
     def forward(self, query, reference_points, feat, spatial_shapes, level_start_index, H, W):
-        qn, qres = ops.layer_norm_res(query, self.query_norm.weight, self.query_norm.bias, self.query_norm.eps)
+        # query_norm and ffn_norm each feed ONE narrow product: LayerNorm + consumer are one autograd node each, so the LayerNorm backward
+        # takes its dy as a product (ops._ln_bwd_of_product)
         fn = ops.layer_norm(feat, self.feat_norm.weight, self.feat_norm.bias, self.feat_norm.eps)
-        query = self.attn(qn, reference_points, fn, spatial_shapes, level_start_index, None, residual=qres)    # ADP:142-145
+        query = self.attn(query, reference_points, fn, spatial_shapes, level_start_index, None, query_norm=self.query_norm)    # ADP:142-145
         if self.with_cffn:
-            f, fres = ops.layer_norm_res(query, self.ffn_norm.weight, self.ffn_norm.bias, self.ffn_norm.eps)
             mask = self.drop_path.mask(query.shape[0], query.device) if isinstance(self.drop_path, DropPath) else None
-            query = self.ffn(f, H, W, residual=fres, row_scale=mask)                                             # ADP:148
+            query = self.ffn(query, H, W, row_scale=mask, norm=self.ffn_norm)                                    # ADP:148
         return query
 
 

@@ -2006,6 +2006,157 @@ def offsets_prep(x, w1, w2, b1, b2, ref, Lq, M, P, Hs, Ws):
 
 
 # ----------------------------------------------------------------------------------------------------
+# LayerNorm (residual hand-through) + its ONLY, narrow consumer as one autograd node
+# ----------------------------------------------------------------------------------------------------
+# The adapter's query_norm feeds only the offsets | weights product (K = 192), its ffn_norm only ConvFFN.fc1 (K = 256).  As two nodes the
+# consumer's data gradient writes dy (rows x 1024) for the LayerNorm backward to read straight back; as one node the backward hands the
+# consumer's output gradient G and W^T to du_layernorm_bwd_prod, which forms dy = bf16(G W) in LDS (csrc/norm_gemm.hip).  The library
+# decides (du_layernorm_bwd_prod_plan); for what it declines the node runs the two kernels of the two-node form, unchanged.
+_LN_BWD_PROD = _ab_env("DINOUNET_LN_BWD_PROD", "1") == "1"      # A-B aid: 0 = data-gradient product + du_layernorm_bwd inside the same nodes
+
+
+class _SubCtx:
+    """stands in for the autograd ctx of a node whose forward / backward a fused node runs as a part of its own"""
+
+    def save_for_backward(self, *ts):
+        self.saved_tensors = ts
+
+    def set_materialize_grads(self, v):
+        pass
+
+
+def layernorm_bwd_prod_plan(xc, G, wT, dx, dres):
+    """du_layernorm_bwd_prod_plan for these tensors -> [served, rows per block, workgroups, rows per workgroup, scratch floats, LDS bytes],
+    or None where the library declines (or the operands are not row matrices with a unit column stride)."""
+    if wT is None or G.dim() != 2 or wT.dim() != 2 or G.stride(1) != 1 or wT.stride(1) != 1 or G.shape[1] != wT.shape[1]:
+        return None
+    if not (xc.is_contiguous() and dx.is_contiguous() and (dres is None or dres.is_contiguous())) or wT.shape[0] != xc.shape[-1]:
+        return None
+    if G.dtype != xc.dtype or wT.dtype != xc.dtype or xc.dtype not in (torch.bfloat16, torch.float32):
+        return None
+    D = xc.shape[-1]
+    out = (C.c_int64 * 6)()
+    rc = _lib.lib().du_layernorm_bwd_prod_plan(_code(xc.dtype), _p(xc), _p(G), G.stride(0), _p(wT), wT.stride(0), G.shape[1], _p(dx), _p(dres),
+                                               xc.numel() // D, D, out, 6)
+    return list(out) if rc == 6 and out[0] == 1 else None
+
+
+def _ln_bwd_of_product(ln_saved, G, wT, wq, dres):
+    """-> (dx, dw, db) of the LayerNorm whose output gradient is the product dy = G wT^T (wT (D, K); wq (K, D) serves where wT is None)."""
+    xc, wf, mean, rstd = ln_saved
+    D = xc.shape[-1]
+    rows = xc.numel() // D
+    dx = torch.empty_like(xc)
+    dwdb = torch.empty((2, D), dtype=torch.float32, device=xc.device)
+    dr = None
+    if dres is not None:
+        dr = dres.contiguous()
+        if dr.dtype != xc.dtype:
+            dr = cast(dr, xc.dtype)
+    L = _lib.lib()
+    plan = layernorm_bwd_prod_plan(xc, G, wT, dx, dr) if _LN_BWD_PROD else None
+    if plan is not None:
+        K = G.shape[1]
+        ws = torch.empty(max(plan[4], 1), dtype=torch.float32, device=xc.device)
+        e0 = PROFILE.start() if PROFILE is not None else None
+        _lib.check(L.du_layernorm_bwd_prod(_code(xc.dtype), _p(xc), _p(G), G.stride(0), _p(wT), wT.stride(0), K, _p(wf), _p(mean), _p(rstd),
+                                           _p(dx), _p(dwdb), rows, D, _p(ws), plan[4], _p(dr), _st()), "du_layernorm_bwd_prod")
+        if PROFILE is not None:     # the product's FLOPs; x, G and dres read once, dx written once
+            PROFILE.stop(f"layernorm_bwd_prod<K{K}>", e0, 2.0 * rows * D * K,
+                         float(xc.element_size() * (rows * D * (3 if dr is not None else 2) + rows * K)))
+        return dx, dwdb[0], dwdb[1]
+    dy = mm(G, wT) if wT is not None else mm_dgrad(G, wq)
+    ws, n = _reduce_ws(xc.dtype, 1, rows, D, xc.device)
+    _lib.check(L.du_layernorm_bwd(_code(xc.dtype), _p(xc), _p(dy), _p(wf), _p(mean), _p(rstd), _p(dx), _p(dwdb), rows, D, _p(ws), n, _p(dr),
+                                  _st()), "du_layernorm_bwd")
+    return dx, dwdb[0], dwdb[1]
+
+
+class _LayerNormLinear(torch.autograd.Function):
+    """(linear(LN(x)), x): _LayerNorm with the residual hand-through + _Linear (no residual, no row scale) as one node.  The forward is the
+    two nodes' forwards; the backward queues the linear layer's weight / bias gradients as _Linear does and leaves the data gradient to
+    _ln_bwd_of_product."""
+
+    @staticmethod
+    def forward(ctx, x, lnw, lnb, eps, w, bias):
+        ln, li = _SubCtx(), _SubCtx()
+        y, xres = _LayerNorm.forward(ln, x, lnw, lnb, eps, True)
+        h = _Linear.forward(li, y.view(-1, y.shape[-1]), w, bias, None, None, 0, None)
+        ctx.save_for_backward(*ln.saved_tensors, *li.saved_tensors[:2])
+        ctx.wT, ctx.wrefs, ctx.has_bias = li.wT, li.wrefs, li.has_bias
+        ctx.set_materialize_grads(False)
+        return h, xres
+
+    @staticmethod
+    def backward(ctx, dh, dres=None):
+        xc, wf, mean, rstd, y, wq = ctx.saved_tensors
+        if dh is None:
+            return dres, None, None, None, None, None
+        G = dh if dh.stride(1) == 1 else dh.contiguous()
+        if G.dtype != y.dtype:
+            G = cast(G, y.dtype)
+        li = _SubCtx()
+        li.saved_tensors = (y, wq, None)
+        li.wT, li.wrefs, li.has_bias, li.has_res, li.rs_rows = ctx.wT, ctx.wrefs, ctx.has_bias, False, 0
+        li.needs_input_grad = (False, ctx.needs_input_grad[4], ctx.needs_input_grad[5])
+        _, dw, db, *_ = _Linear.backward(li, G)
+        dx, dlw, dlb = _ln_bwd_of_product((xc, wf, mean, rstd), G, ctx.wT, wq, dres)
+        return dx, dlw, dlb, None, dw, db
+
+
+def layer_norm_linear(x, lnw, lnb, eps, w, bias=None):
+    """-> (linear(LN(x)), x): the second output is the block's residual (see layer_norm_res)."""
+    if not x.is_cuda:         # no device tensor, no fused node: the two ops it is made of, as this module names them at call time
+        f, xres = layer_norm_res(x, lnw, lnb, eps)
+        return linear(f, w, bias), xres
+    h, xres = _LayerNormLinear.apply(x, lnw, lnb, eps, w, bias)
+    return h.view(*x.shape[:-1], w.shape[0]), xres
+
+
+class _LayerNormOffsetsPrep(torch.autograd.Function):
+    """(loc, attn, x): _LayerNorm with the residual hand-through + _OffsetsPrep as one node (see _LayerNormLinear)."""
+
+    @staticmethod
+    def forward(ctx, x, lnw, lnb, eps, w1, w2, b1, b2, ref, Lq, M, P, Hs, Ws):
+        ln, op = _SubCtx(), _SubCtx()
+        y, xres = _LayerNorm.forward(ln, x, lnw, lnb, eps, True)
+        loc, attn = _OffsetsPrep.forward(op, y.view(-1, y.shape[-1]), w1, w2, b1, b2, ref, Lq, M, P, Hs, Ws)
+        ctx.save_for_backward(*ln.saved_tensors, *op.saved_tensors)
+        ctx.wT, ctx.wrefs, ctx.conf, ctx.prep = op.wT, op.wrefs, op.conf, op.prep
+        ctx.set_materialize_grads(False)
+        return loc, attn, xres
+
+    @staticmethod
+    def backward(ctx, gloc, gattn, dres=None):
+        xc, wf, mean, rstd, y, wq, attn = ctx.saved_tensors
+        if gloc is None and gattn is None:
+            return (dres,) + (None,) * 13
+        if gloc is None:
+            gloc = torch.zeros((*attn.shape, 2), dtype=torch.float32, device=attn.device)
+        if gattn is None:
+            gattn = torch.zeros_like(attn)
+        M, P, Hs, Ws, ncol = ctx.prep
+        rows = attn.shape[0]
+        graw = torch.empty((rows, ncol), dtype=y.dtype, device=attn.device)
+        _lib.check(_lib.lib().du_msda_prep_bwd(_code(y.dtype), _p(attn), _p(gloc.contiguous()), _p(gattn.contiguous()), _p(graw), ncol, rows,
+                                               M, P, Hs, Ws, _st()), "du_msda_prep_bwd")
+        op = _SubCtx()
+        op.wT, op.wrefs, op.conf = ctx.wT, ctx.wrefs, ctx.conf
+        op.needs_input_grad = (False,)
+        _, dw1, dw2, db1, db2 = _linear_cat_bwd(op, graw, y, wq)
+        dx, dlw, dlb = _ln_bwd_of_product((xc, wf, mean, rstd), graw, ctx.wT, wq, dres)
+        return dx, dlw, dlb, None, dw1, dw2, db1, db2, None, None, None, None, None, None
+
+
+def layer_norm_offsets_prep(x, lnw, lnb, eps, w1, w2, b1, b2, ref, Lq, M, P, Hs, Ws):
+    """(N, Lq, C) un-normalised queries -> (loc, attn, x): offsets_prep(LN(x)) and the residual hand-through of layer_norm_res."""
+    if not x.is_cuda:         # (see layer_norm_linear)
+        q, xres = layer_norm_res(x, lnw, lnb, eps)
+        return (*offsets_prep(q, w1, w2, b1, b2, ref, Lq, M, P, Hs, Ws), xres)
+    return _LayerNormOffsetsPrep.apply(x, lnw, lnb, eps, w1, w2, b1, b2, ref, Lq, M, P, Hs, Ws)
+
+
+# ----------------------------------------------------------------------------------------------------
 # small NHWC ops
 # ----------------------------------------------------------------------------------------------------
 def _dwconv_fwd(ctx, x, w, bias, geom, act):

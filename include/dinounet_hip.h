@@ -295,6 +295,20 @@ int64_t du_reduce_ws_elems(int dtype, int G, int64_t pix_per_group, int C);
    dres (nullable, same dtype/shape as x): gradient of a residual branch that by-passes the norm, added into dx. */
 int du_layernorm_bwd(int dtype, const void* x, const void* dy, const float* w, const float* mean, const float* rstd,
                      void* dx, float* dwdb, int64_t rows, int D, float* ws, int64_t ws_elems, const void* dres, void* stream);
+/* du_layernorm_bwd whose dy is a narrow product that is never written: dy = bf16(G Wt^T) with fp32 accumulation and one rounding -- G
+   (rows, K) bf16 with row stride ldg, Wt (D, K) bf16 with row stride ldw (the K-contiguous operand of the unfused data gradient) -- then the
+   arithmetic of du_layernorm_bwd on dense (rows, D) x / dx / dres (csrc/norm_gemm.hip: a workgroup owns whole rows and keeps their dy in
+   LDS).  dwdb: PLANAR dw[D] then db[D]; the scratch is required, out[4] of the plan in floats.
+   The library decides once per call (csrc/norm_gemm_plan.h): bf16, D == 1024, K % 64 == 0 and K <= 256, ldg / ldw multiples of 8 and >= K,
+   x / G / Wt / dx / dres 16-byte aligned; every other call is DU_ERR_UNSUPPORTED before anything launches and the caller runs the data
+   gradient and du_layernorm_bwd.  _plan reads the same decision from the call's numbers alone (no operand is dereferenced):
+   out[0..5] = {served (1 / 0), rows per block, workgroups, rows per workgroup, scratch floats, LDS bytes}; returns 6, DU_ERR_BAD_ARG for
+   out == NULL or n < 6. */
+int du_layernorm_bwd_prod_plan(int dtype, const void* x, const void* G, int64_t ldg, const void* Wt, int64_t ldw, int K, const void* dx,
+                               const void* dres, int64_t rows, int D, int64_t* out, int n);
+int du_layernorm_bwd_prod(int dtype, const void* x, const void* G, int64_t ldg, const void* Wt, int64_t ldw, int K, const float* w,
+                          const float* mean, const float* rstd, void* dx, float* dwdb, int64_t rows, int D, float* ws, int64_t ws_elems,
+                          const void* dres, void* stream);
 
 /* ---- channel-statistics norms (InstanceNorm2d / BatchNorm2d over NHWC) ---------------------------- */
 /* sums[g][c][0..1] += (sum x, sum x^2) over the pixels of group g (G groups of `pix_per_group` pixels). */
