@@ -338,12 +338,18 @@ class DINOv3_Adapter(nn.Module):
         if isinstance(m, MSDeformAttn):
             m._reset_parameters()
 
-    def forward(self, x):
-        """x: (B, 3, H, W) fp32 NCHW.  Returns {"1".."4"}: NHWC feature maps (B, H/4.., W/4.., D) in the activation dtype."""
+    def forward(self, x, layers=None):
+        """x: (B, 3, H, W) fp32 NCHW.  Returns {"1".."4"}: NHWC feature maps (B, H/4.., W/4.., D) in the activation dtype.
+        layers: what backbone_layers(x) returned for this x; the frozen backbone is then not launched (fold ensembles share one pass)."""
         with _collect_ticks():
-            return self._forward(x)
+            return self._forward(x, layers)
 
-    def _forward(self, x):
+    def backbone_layers(self, x):
+        """The intermediate layers of the frozen backbone that _forward reads, for x (B, 3, H, W) fp32, complete on the caller's stream when
+        this returns.  They do not depend on the adapter's own parameters."""
+        return self.backbone.get_intermediate_layers(x, n=self.interaction_indexes, return_class_token=True, dtype=_act_dtype(self))
+
+    def _forward(self, x, layers=None):
         dt = _act_dtype(self)
         B, _, H, W = x.shape
         D = self.backbone.embed_dim
@@ -370,7 +376,7 @@ class DINOv3_Adapter(nn.Module):
         # The frozen backbone is launched FIRST (ADP:422-426): with `backbone.chains` > 1 it runs as half-batch chains on side streams and the
         # spatial prior module below -- independent of it (ADP:412-415), HBM-bound where the ViT is MFMA-bound -- runs beside them on this
         # stream; `vit()` joins the chains.  (chains <= 1: the backbone simply runs before the prior module; same results either way.)
-        chained = getattr(self.backbone, "chains", 1) > 1
+        chained = layers is None and getattr(self.backbone, "chains", 1) > 1
         if chained:
             vit = self.backbone.begin_intermediate_layers(x, n=self.interaction_indexes, return_class_token=True, dtype=dt)
             if not getattr(self.backbone, "overlap_prior", True):
@@ -383,7 +389,7 @@ class DINOv3_Adapter(nn.Module):
 
         if chained:
             layers = vit()
-        else:       # one chain on this stream: the reference's order (prior module, then the backbone, ADP:412-426)
+        elif layers is None:       # one chain on this stream: the reference's order (prior module, then the backbone, ADP:412-426)
             layers = self.backbone.get_intermediate_layers(x, n=self.interaction_indexes, return_class_token=True, dtype=dt)
 
         for i, layer in enumerate(self.interactions):                                       # ADP:444-457

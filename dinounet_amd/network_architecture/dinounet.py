@@ -213,14 +213,24 @@ class DINOv3EncoderAdapter(nn.Module):
         self.strides = [[2, 2]] * len(target_channels)
         self.kernel_sizes = [[3, 3]] * len(target_channels)
 
-    def forward(self, x):
-        """x (B, C, H, W) fp32 NCHW -> 4 NHWC skips (DT:489-511)."""
-        B, C, H, W = x.shape
+    @staticmethod
+    def _three_channels(x):
+        C = x.shape[1]
         if C == 1:
             x = x.repeat(1, 3, 1, 1)
         elif C != 3:
             x = x.repeat(1, 3 // C + (1 if 3 % C != 0 else 0), 1, 1)[:, :3] if C < 3 else x[:, :3]
-        feats = self.dinov3_adapter(x)
+        return x
+
+    def backbone_layers(self, x):
+        """the frozen backbone's layers for x (B, C, H, W) fp32, with the channel handling of forward; pass them back as forward(x, layers)"""
+        return self.dinov3_adapter.backbone_layers(self._three_channels(x))
+
+    def forward(self, x, layers=None):
+        """x (B, C, H, W) fp32 NCHW -> 4 NHWC skips (DT:489-511).  layers: backbone_layers(x); the backbone is then not launched."""
+        B, C, H, W = x.shape
+        x = self._three_channels(x)
+        feats = self.dinov3_adapter(x) if layers is None else self.dinov3_adapter(x, layers)
         ys = self.fapm([feats[k] for k in ("1", "2", "3", "4")])
         return [self.ups[i](y, (H // (2 ** i), W // (2 ** i))) for i, y in enumerate(ys)]
 
@@ -439,13 +449,24 @@ class DinoUNet(nn.Module):
     # the C ABI (raw pointers, ctypes), nothing dynamo can trace -- it is excluded from tracing, so the compiled wrapper runs this very
     # code (same logits, same gradients; tests/test_gpu_boundary.py::test_torch_compile_wrapper_keeps_logits)
     @torch.compiler.disable
-    def forward(self, x):
+    def forward(self, x, vit_layers=None):
+        """vit_layers: backbone_layers(x) of this or of another DinoUNet that shares the frozen backbone; the backbone is then not launched"""
         if not x.is_cuda:
             raise RuntimeError("DinoUNet (dinounet_amd) runs on the MI355X through libdinounet_hip.so; move the module and "
                                "its input to the GPU (there is no CPU fallback)")
         ops.PACK.refresh()          # one launch: kernel-ready bf16 forms of every trainable weight for this step
         ops.ZEROS.new_step()        # one fill: the fp32 accumulators of this step's split-K weight gradients
-        return self.decoder(self.encoder(x.float()))
+        if vit_layers is None:
+            return self.decoder(self.encoder(x.float()))
+        return self.decoder(self.encoder(x.float(), vit_layers))
+
+    @torch.compiler.disable
+    def backbone_layers(self, x):
+        """The frozen backbone's intermediate layers for an input batch x (B, C, H, W), on the caller's stream: what forward(x, vit_layers=...)
+        takes.  Every fold of a model carries the same frozen backbone, so one such pass serves the heads of all of them."""
+        if not x.is_cuda:
+            raise RuntimeError("DinoUNet (dinounet_amd) runs on the MI355X through libdinounet_hip.so (there is no CPU fallback)")
+        return self.encoder.backbone_layers(x.float())
 
     def compute_conv_feature_map_size(self, input_size):
         return 0

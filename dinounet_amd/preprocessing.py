@@ -547,12 +547,19 @@ def run_case_from_plans(data, seg, properties, plans, configuration_name):
 
 @torch.no_grad()
 def predict_from_raw(net, data, properties, patch_size, *, transpose_forward, spacing, normalization_schemes, use_mask_for_norm,
-                     foreground_intensity_properties_per_channel, **predict_kwargs):
+                     foreground_intensity_properties_per_channel, list_of_parameters=None, **predict_kwargs):
     """Raw array in, label map in the raw geometry out: run_case(data, None, properties, ...), then export.predict_segmentation on the
     preprocessed image with `properties` and transpose_backward = the inverse of transpose_forward.  predict_kwargs are those of
     predict_segmentation (tile_step_size, use_gaussian, batch_size, graph, mirror_axes, regions_class_order, return_probabilities).
-    Returns the uint8 label map of data's spatial shape on the network's device (with return_probabilities: and the probabilities)."""
+    Returns the uint8 label map of data's spatial shape on the network's device (with return_probabilities: and the probabilities).
+    Fold ensembles: `net` may be an inference.EnsemblePredictor, or list_of_parameters holds the folds' parameter sets for `net` (a
+    predictor is then built for this call; keep one yourself to predict many cases)."""
     from .export import predict_segmentation
+    from .inference import EnsemblePredictor
+    if list_of_parameters is not None:
+        if isinstance(net, EnsemblePredictor):
+            raise ValueError("list_of_parameters goes with a network, not with an EnsemblePredictor")
+        net = EnsemblePredictor(net, list_of_parameters)
     for k in ("properties", "transpose_backward"):
         if k in predict_kwargs:
             raise ValueError(f"predict_from_raw derives {k} itself")
@@ -561,4 +568,6 @@ def predict_from_raw(net, data, properties, patch_size, *, transpose_forward, sp
                       use_mask_for_norm=use_mask_for_norm,
                       foreground_intensity_properties_per_channel=foreground_intensity_properties_per_channel)
     transpose_backward = [tf.index(i) for i in range(3)]
+    if isinstance(net, EnsemblePredictor):
+        return net.predict_segmentation(pre, patch_size, properties=properties, transpose_backward=transpose_backward, **predict_kwargs)
     return predict_segmentation(net, pre, patch_size, properties=properties, transpose_backward=transpose_backward, **predict_kwargs)

@@ -40,6 +40,8 @@
  *   du_export_seg, du_seg_counts
  *       <- convert_predicted_logits_to_segmentation_with_correct_shape (inference/export_prediction.py:15-68) and
  *          compute_metrics' counts (evaluation/evaluate_predictions.py:75-94, 176-186)
+ *   du_ensemble_merge
+ *       <- average_probabilities and merge_files (ensembling/ensemble.py:17-46)
  *   du_surface_border, du_surface_field, du_surface_gather
  *       <- compute_surface_distances (evaluation/evaluate_predictions.py:97-149): medpy.metric.hd95 / asd, restated
  */
@@ -645,6 +647,19 @@ int du_export_seg(const float* sums, const float* npred, uint8_t* seg, float* pr
 int64_t du_seg_counts_ws_elems(int64_t n, int R);
 int du_seg_counts(const uint8_t* pred, const uint8_t* ref, const int64_t* masks, int64_t* counts, int64_t n, int R, int has_ignore,
                   int ignore_label, int32_t* ws, int64_t ws_elems, void* stream);
+
+/* ---- ensembling: M member probability volumes -> label map (+ the averaged probabilities), ONE pass (csrc/ensemble.hip;
+   average_probabilities and merge_files, dinounet/ensembling/ensemble.py:17-46).  members: DEVICE table of M (1..16) pointers, each to a
+   contiguous (K, n) array, all fp32 (elem_size 4) or all fp16 (elem_size 2); a member may start at any element.
+   mean (K, n) fp32 or NULL = (((p0 + p1) + p2) + ...) / M in fp32, members in table order, one correctly rounded division: equal to numpy's
+   `avg += p; avg /= M` to the bit for finite inputs.  seg (n) uint8 or NULL (then K may be 1 in either mode): DU_EXPORT_SOFTMAX (K in [2,8])
+   the lowest index among the maxima of the mean; DU_EXPORT_REGIONS (K = R in [1,8]) byte i of region_order painted where mean_i > 0.5, in
+   order (convert_probabilities_to_segmentation, label_handling.py:143-175).  flag (DEVICE int32, zeroed by the caller) = 1 if a mean is
+   not finite (a non-finite member always makes one).  16-byte loads when every member pointer is on 16 bytes, n is a multiple of
+   16 / elem_size and seg / mean are aligned likewise; guarded element accesses otherwise.  DU_ERR_UNSUPPORTED: M, K, elem_size out of
+   range or n < 0; DU_ERR_BAD_ARG: a NULL table or flag, neither seg nor mean, an unknown mode. */
+int du_ensemble_merge(const void* const* members, int M, int elem_size, int K, int64_t n, int mode, int64_t region_order, uint8_t* seg,
+                      float* mean, int32_t* flag, void* stream);
 
 /* ---- fused clip_grad_norm_ + Nesterov SGD over all trainable tensors (replaces
    torch.nn.utils.clip_grad_norm_(params, 12) + torch.optim.SGD.step(), dinounet/training/nnUNetTrainer/nnUNetTrainer.py:486,922-924).
