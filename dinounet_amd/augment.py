@@ -20,6 +20,14 @@ oracle/augment_oracle.py).  Order and probabilities:
     Gamma              p 0.3, same
     Mirror             each axis with p 0.5
     RemoveLabel(-1,0)  (out-of-image labels are already 0)
+
+Two interpolation modes.  The default "keys" resamples the image with the Keys bicubic kernel and counts an in-image label -1 as "outside
+the image" (csrc/augment.hip).  "spline" computes what batchgenerators computes (csrc/augment_spline.hip): the image by
+scipy's map_coordinates(order=3, mode="constant") -- prefiltered cubic B-spline, fp64, one rounding --, samples that drew neither rotation
+nor scale by the integer centre crop, labels with -1 as a label of its own, the low-resolution simulation's up-sampling by skimage's resize
+(scipy zoom order 3, mode "nearest", grid_mode, clipped), and MaskTransform (mask_channels) + RemoveLabel(-1, 0) as the last pass.  Both
+modes draw the same random numbers in the same order.  The `_*_numpy` functions restate the spline-mode device algorithms on the host in
+fp64; tests/test_cpu_augment_spline.py checks them against scipy.
 """
 import ctypes as C
 
@@ -37,10 +45,188 @@ def _st():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ---- host restatements of csrc/augment_spline.hip (fp64) -------------------------------------------------------------------------
+_HORIZON = 32                       # the prefilter sqrt(3) z^|k|, z = sqrt(3) - 2, is cut at |k| <= 32: |z|^33 < 2e-19
+
+
+def _mirror(i, n):
+    """scipy's "mirror" extension (d c b | a b c d | c b a) of indices at any distance from a line of n samples"""
+    if n == 1:
+        return np.zeros_like(i)
+    p = 2 * (n - 1)
+    i = np.abs(i) % p
+    return np.where(i >= n, p - i, i)
+
+
+def _bspline_weights(t):
+    u = 1.0 - t
+    return (u * u * u / 6.0, (4.0 - 6.0 * t * t + 3.0 * t * t * t) / 6.0, (4.0 - 6.0 * u * u + 3.0 * u * u * u) / 6.0, t * t * t / 6.0)
+
+
+def _is_identity(prm):
+    """no rotation and no scale were drawn: the matrix part is exactly [1, 0, 0, 1]"""
+    return bool(prm[0] == 1 and prm[1] == 0 and prm[2] == 0 and prm[3] == 1)
+
+
+def _spline_coeffs_numpy(x):
+    """cubic B-spline coefficients of the plane x along both axes (scipy.ndimage.spline_filter(x, 3, mode="mirror")), no padding"""
+    c = np.asarray(x, np.float64)
+    k = np.arange(-_HORIZON, _HORIZON + 1)
+    w = np.sqrt(3.0) * (np.sqrt(3.0) - 2.0) ** np.abs(k)
+    for _ in range(2):                                                              # along x, then along y: filter axis 1, transpose
+        n = c.shape[1]
+        if n > 1:                                                                   # a line of length 1 is its own coefficient
+            c = (c[:, _mirror(np.arange(n)[:, None] + k[None, :], n)] * w).sum(2)
+        c = c.T
+    return c
+
+
+def _coords_float64(prm, Hi, Wi, Ho, Wo):
+    """input coordinates of the output pixels, MirrorTransform folded in: the six fp32 parameters of one sample, then fp64 throughout
+    (batchgenerators' zero-centred mesh, rotation and scale as one matrix, + the input's centre)"""
+    ys, xs = np.meshgrid(np.arange(Ho, dtype=np.float64), np.arange(Wo, dtype=np.float64), indexing="ij")
+    if prm[4]:
+        ys = Ho - 1 - ys
+    if prm[5]:
+        xs = Wo - 1 - xs
+    m = np.asarray(prm[:4], np.float32).astype(np.float64)
+    cy, cx = ys - 0.5 * (Ho - 1), xs - 0.5 * (Wo - 1)
+    return m[0] * cy + m[1] * cx + (Hi / 2.0 - 0.5), m[2] * cy + m[3] * cx + (Wi / 2.0 - 0.5)
+
+
+def _centre_crop(x, prm, patch):
+    """what an identity sample gets: rows / columns (n_in - n_out) // 2 onwards, flipped"""
+    Ho, Wo = patch
+    y0, x0 = (x.shape[-2] - Ho) // 2, (x.shape[-1] - Wo) // 2
+    out = x[..., y0:y0 + Ho, x0:x0 + Wo]
+    if prm[4]:
+        out = out[..., ::-1, :]
+    if prm[5]:
+        out = out[..., :, ::-1]
+    return out
+
+
+def _spatial_spline_numpy(data, prm, patch):
+    """SpatialTransform + MirrorTransform on the image as du_aug_spatial_spline computes it: data (B, C, Hi, Wi) -> float64 (B, C, *patch)
+    (the device result is this rounded to fp32).  Identity samples are cropped; the others are map_coordinates(order=3, mode="constant",
+    cval=0): 0 outside [0, Hi - 1] x [0, Wi - 1], else the 4 x 4 B-spline sum over the mirror-prefiltered coefficients, taps mirrored."""
+    B, Cc, Hi, Wi = data.shape
+    Ho, Wo = patch
+    out = np.zeros((B, Cc, Ho, Wo), np.float64)
+    for b in range(B):
+        if _is_identity(prm[b]):
+            out[b] = _centre_crop(np.asarray(data[b], np.float64), prm[b], patch)
+            continue
+        y, x = _coords_float64(prm[b], Hi, Wi, Ho, Wo)
+        inside = (y >= 0) & (y <= Hi - 1) & (x >= 0) & (x <= Wi - 1)
+        y0, x0 = np.floor(y).astype(np.int64), np.floor(x).astype(np.int64)
+        wy, wx = _bspline_weights(y - y0), _bspline_weights(x - x0)
+        for c in range(Cc):
+            coef = _spline_coeffs_numpy(data[b, c])
+            acc = np.zeros((Ho, Wo))
+            for j in range(4):
+                row = np.zeros((Ho, Wo))
+                for i in range(4):
+                    row += wx[i] * coef[_mirror(y0 - 1 + j, Hi), _mirror(x0 - 1 + i, Wi)]
+                acc += wy[j] * row
+            out[b, c] = np.where(inside, acc, 0.0)
+    return out
+
+
+def _labels_order1_numpy(seg, prm, patch):
+    """the labels of du_aug_spatial_spline BEFORE the mask pass: seg (B, 1, Hi, Wi) -> float64 (B, 1, *patch), -1 possible.  Identity
+    samples are cropped.  Otherwise 0 outside the image; inside, the largest label (-1 included) whose four bilinear taps carry a weight
+    >= 1/2, else 0: batchgenerators' interpolate_img(is_seg=True, order=1, cval=-1) on every one-hot map, ascending labels overwriting."""
+    B, _, Hi, Wi = seg.shape
+    Ho, Wo = patch
+    out = np.zeros((B, 1, Ho, Wo), np.float64)
+    for b in range(B):
+        s = np.asarray(seg[b, 0], np.float64)
+        if _is_identity(prm[b]):
+            out[b, 0] = _centre_crop(s, prm[b], patch)
+            continue
+        y, x = _coords_float64(prm[b], Hi, Wi, Ho, Wo)
+        inside = (y >= 0) & (y <= Hi - 1) & (x >= 0) & (x <= Wi - 1)
+        y0, x0 = np.clip(np.floor(y).astype(np.int64), 0, Hi - 1), np.clip(np.floor(x).astype(np.int64), 0, Wi - 1)
+        fy, fx = y - y0, x - x0
+        y1, x1 = np.minimum(y0 + 1, Hi - 1), np.minimum(x0 + 1, Wi - 1)           # weight 0 where clamped
+        w = [(1 - fy) * (1 - fx), (1 - fy) * fx, fy * (1 - fx), fy * fx]
+        lab = [s[y0, x0], s[y0, x1], s[y1, x0], s[y1, x1]]
+        best, found = np.zeros((Ho, Wo)), np.zeros((Ho, Wo), bool)
+        for k in range(4):
+            total = np.zeros((Ho, Wo))
+            for m_ in range(4):
+                total += np.where(lab[m_] == lab[k], w[m_], 0.0)
+            take = (total >= 0.5) & (~found | (lab[k] > best))
+            best = np.where(take, lab[k], best)
+            found |= take
+        out[b, 0] = np.where(inside, best, 0.0)
+    return out
+
+
+def _lowres_sizes(zoom, H, W):
+    """(P, 2) int32 low grids of SimulateLowResolutionTransform, max(rint(size * zoom), 1) in fp32 as du_aug_lowres; (0, 0) = plane left alone"""
+    z = np.asarray(zoom, np.float32).reshape(-1)
+    on = (z > 0) & (z < 1)
+    hl = np.maximum(np.rint(np.float32(H) * z), 1).astype(np.int32)
+    wl = np.maximum(np.rint(np.float32(W) * z), 1).astype(np.int32)
+    return np.stack([np.where(on, hl, 0), np.where(on, wl, 0)], 1).astype(np.int32)
+
+
+def _nearest_src(nl, n):
+    """source pixels of the nl low-grid samples of a line of n: floor((i + 1/2) n / nl), in the fp64 operations of scipy's
+    zoom(order=0, mode="nearest", grid_mode=True) -- where that quotient is an integer, the rounding of n / nl picks the pixel"""
+    cc = ((np.arange(nl, dtype=np.float64) + 0.5) * (n / nl) - 0.5) + 0.5
+    return np.clip(np.floor(cc).astype(np.int64), 0, n - 1)
+
+
+def _lowres_spline_numpy(x, zoom):
+    """SimulateLowResolutionTransform as du_aug_lowres_spline computes it: x (B, C, H, W) -> float64.  Down by the nearest source pixel
+    (_nearest_src), up by preprocessing._resize_cubic_float64 (scipy zoom order 3, mode "nearest", grid_mode), clipped to the low
+    grid's range (skimage's clip=True).  Planes with zoom outside (0, 1) are untouched."""
+    from .preprocessing import _resize_cubic_float64
+    B, Cc, H, W = x.shape
+    out = np.asarray(x, np.float64).copy()
+    sizes = _lowres_sizes(zoom, H, W).reshape(B, Cc, 2)
+    for b in range(B):
+        for c in range(Cc):
+            Hl, Wl = (int(v) for v in sizes[b, c])
+            if Hl == 0:
+                continue
+            low = out[b, c][np.ix_(_nearest_src(Hl, H), _nearest_src(Wl, W))]
+            out[b, c] = np.clip(_resize_cubic_float64(low, (H, W)), low.min(), low.max())
+    return out
+
+
+def _mask_numpy(data, labels, mask_channels):
+    """MaskTransform + RemoveLabelTransform(-1, 0): (data with the masked channels 0 where labels < 0, labels with the negatives 0)"""
+    data, neg = np.array(data), np.asarray(labels)[:, 0] < 0
+    for c in mask_channels:
+        data[:, c][neg] = 0
+    return data, np.where(np.asarray(labels) < 0, 0, labels)
+
+
+def _channel_list(mask_channels):
+    """channel indices from a list of indices or a list of bools (use_mask_for_norm)"""
+    m = list(mask_channels)
+    if all(isinstance(v, (bool, np.bool_)) for v in m):
+        return [i for i, v in enumerate(m) if v]
+    return sorted({int(v) for v in m})
+
+
 class GPUAugment2D:
-    def __init__(self, patch_size, seed=None):
+    def __init__(self, patch_size, seed=None, *, interpolation="keys", mask_channels=None):
         self.patch = tuple(int(v) for v in patch_size)
         assert len(self.patch) == 2
+        if interpolation not in ("keys", "spline"):
+            raise ValueError(f"interpolation must be 'keys' or 'spline', not {interpolation!r}")
+        self.interpolation = interpolation
+        self.mask_channels = (None if mask_channels is None else _channel_list(mask_channels)) or None       # no channel named: no MaskTransform
+        if self.mask_channels is not None and interpolation != "spline":
+            raise ValueError("mask_channels needs interpolation='spline': the Keys path cannot produce the label -1 that MaskTransform reads")
+        if self.mask_channels is not None and any(c < 0 or c > 62 for c in self.mask_channels):
+            raise ValueError("mask_channels must lie in 0 .. 62")
+        self._keep_raw_labels, self._raw_labels = False, None                     # tests: the labels before the mask pass
         lim = 15.0 if max(self.patch) / min(self.patch) > 1.5 else 180.0            # nnUNetTrainer.py:401-412
         self.angle = (-lim / 360 * 2 * np.pi, lim / 360 * 2 * np.pi)
         self.rs = np.random.RandomState(seed)
@@ -119,7 +305,29 @@ class GPUAugment2D:
         ones = np.ones((B, Cc), np.float32)
         t_sp, t_noise, t_one, t_zero = dv(d["spatial"]), dv(d["noise_sigma"]), dv(ones), dv(0 * ones)
         t_blur, t_mult, t_con, t_zoom = dv(d["blur_sigma"]), dv(d["mult"]), dv(d["contrast"]), dv(d["zoom"])
-        _lib.check(L.du_aug_spatial(_p(data), _p(seg), _p(t_sp), _p(out), _p(sout), B, Cc, Hi, Wi, H, W, _st()), "du_aug_spatial")
+        spline = self.interpolation == "spline"
+        if spline:
+            if self.mask_channels and self.mask_channels[-1] >= Cc:
+                raise ValueError(f"mask_channels {self.mask_channels} for {Cc} channels")
+            if self.mask_channels and seg is None:
+                raise ValueError("mask_channels needs the segmentation: MaskTransform zeroes the channels where the resampled label is negative")
+            di = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+            # coefficients only for the planes of samples that drew a rotation or a scale; the others are cropped
+            moved = [b for b in range(B) if not _is_identity(d["spatial"][b])]
+            planes = np.array([b * Cc + c for b in moved for c in range(Cc)], np.int32)
+            slots = np.full(B * Cc, -1, np.int32)
+            slots[planes] = np.arange(len(planes), dtype=np.int32)
+            n_ws = int(L.du_aug_spline_ws_elems(max(len(planes), 1), Hi, Wi))
+            if n_ws < 0:
+                _lib.check(n_ws, "du_aug_spline_ws_elems")
+            coef = torch.empty(n_ws, dtype=torch.float64, device=dev)
+            t_planes, t_slots = di(planes if len(planes) else [0]), di(slots)
+            if len(planes):
+                _lib.check(L.du_aug_spline_coeffs(_p(data), B * Cc, _p(t_planes), len(planes), Hi, Wi, _p(coef), n_ws, _st()), "du_aug_spline_coeffs")
+            _lib.check(L.du_aug_spatial_spline(_p(data), _p(seg), _p(t_sp), _p(coef), len(planes), _p(t_slots), _p(out), _p(sout), B, Cc, Hi, Wi,
+                                               H, W, _st()), "du_aug_spatial_spline")
+        else:
+            _lib.check(L.du_aug_spatial(_p(data), _p(seg), _p(t_sp), _p(out), _p(sout), B, Cc, Hi, Wi, H, W, _st()), "du_aug_spatial")
         P, n = B * Cc, H * W
         tmp = torch.empty_like(out)
         stats = torch.empty((P, 4), dtype=torch.float32, device=dev)
@@ -133,7 +341,13 @@ class GPUAugment2D:
             _lib.check(L.du_aug_plane_stats(_p(out), _p(stats), P, n, _st()), "du_aug_plane_stats")
             _lib.check(L.du_aug_contrast(_p(out), _p(t_con), _p(stats), P, n, _st()), "du_aug_contrast")
         if ((d["zoom"] > 0) & (d["zoom"] < 1)).any():
-            _lib.check(L.du_aug_lowres(_p(out), _p(tmp), _p(t_zoom), P, H, W, _st()), "du_aug_lowres")
+            if spline:
+                t_sizes = di(_lowres_sizes(d["zoom"], H, W))
+                t_bounds = torch.empty((P, 32, 2), dtype=torch.float32, device=dev)
+                t_mid = torch.empty(P * n, dtype=torch.float64, device=dev)
+                _lib.check(L.du_aug_lowres_spline(_p(out), _p(tmp), _p(t_sizes), _p(t_bounds), _p(t_mid), P, H, W, _st()), "du_aug_lowres_spline")
+            else:
+                _lib.check(L.du_aug_lowres(_p(out), _p(tmp), _p(t_zoom), P, H, W, _st()), "du_aug_lowres")
             out, tmp = tmp, out
         keep = []                      # operands of the asynchronous launches below stay referenced until apply() returns
         for key, inv in (("gamma_inv", 1.0), ("gamma", 0.0)):
@@ -155,6 +369,12 @@ class GPUAugment2D:
             bb = ((bb * sgn) * onv).contiguous()
             _lib.check(L.du_aug_affine(_p(out), _p(a), _p(bb), P, n, _st()), "du_aug_affine")
             keep += [t_g, t_inv, onv, a, bb, before]
+        if spline and sout is not None:
+            # MaskTransform after every intensity transform, then RemoveLabel(-1, 0): the spline path's labels may hold -1
+            if self._keep_raw_labels:
+                self._raw_labels = sout.clone()
+            bits = sum(1 << c for c in (self.mask_channels or []))
+            _lib.check(L.du_aug_mask(_p(out), _p(sout), bits, B, Cc, n, _st()), "du_aug_mask")
         return out, sout
 
     def __call__(self, data, seg=None):

@@ -6,6 +6,8 @@
 // UNPINNED against that package; each kernel restates the package's published algorithm and is tested against a numpy / scipy
 // restatement (oracle/augment_oracle.py).  One documented deviation: image resampling uses the Keys bicubic kernel (a = -0.5) where
 // batchgenerators calls scipy.ndimage.map_coordinates(order=3) (cubic B-spline with prefilter); the two agree to O(h^3) on smooth data.
+// The deviation is closed by GPUAugment2D(interpolation="spline"): augment_spline.hip computes what scipy computes, there also for the
+// label -1 inside the image, the low-resolution simulation and MaskTransform.  The kernels of this file are the default and stay as they are.
 //
 //   du_aug_spatial      SpatialTransform (rotation, isotropic scale, centre crop) + MirrorTransform folded into one resampling pass;
 //                       labels follow batchgenerators' order-1 rule (per label: bilinear interpolation of its one-hot map >= 0.5 with

@@ -441,10 +441,15 @@ class TrainBatches:
     such a pixel as 0 in the other labels' one-hot maps.  A pixel with bilinear weight w on label c and v on padding is c there when
     w >= 1/2 and here when w - v >= 1/2; everywhere else both give 0 after RemoveLabel(-1, 0).  The difference is confined to the
     one-pixel seam between image and padding, where a label can be one pixel narrower here.  du_aug_spatial is existing behaviour and
-    is left as it is."""
+    is left as it is.  With interpolation="spline" the seam is absent: du_aug_spatial_spline treats -1 as a label of
+    its own, as batchgenerators does.
+
+    interpolation and use_mask_for_norm (one bool per channel, or channel indices) go to GPUAugment2D(interpolation=..., mask_channels=...):
+    "spline" resamples as batchgenerators does, and the masked channels are 0 wherever the resampled segmentation is negative."""
 
     def __init__(self, dataset, patch_size, batch_size, oversample_foreground_percent=0.33, all_labels=None, regions=None, ignore_label=None,
-                 seed=None, rank=0, world=1, val=False, sampling_probabilities=None, probabilistic_oversampling=False):
+                 seed=None, rank=0, world=1, val=False, sampling_probabilities=None, probabilistic_oversampling=False, interpolation="keys",
+                 use_mask_for_norm=None):
         from .augment import GPUAugment2D
         self.patch_size = tuple(int(v) for v in patch_size)
         self.val = bool(val)
@@ -457,7 +462,8 @@ class TrainBatches:
         self.loader = DataLoader2D(dataset, self.batch_size, loader_patch, self.patch_size, () if all_labels is None else all_labels,
                                    self.ignore_label is not None, self.oversample_foreground_percent, sampling_probabilities,
                                    probabilistic_oversampling, seed=seed, seg_float=not self.val)
-        self.augment = None if self.val else GPUAugment2D(self.patch_size, seed=None if seed is None else int(seed) + 1)
+        self.augment = None if self.val else GPUAugment2D(self.patch_size, seed=None if seed is None else int(seed) + 1,
+                                                          interpolation=interpolation, mask_channels=use_mask_for_norm)
         dev = next(iter(dataset.values()))[0].device
         self.table = None
         if self.regions is not None and dev.type == "cuda":

@@ -565,6 +565,29 @@ int du_aug_affine(float* x, const float* a, const float* b, int planes, int64_t 
 int du_aug_blur(const float* x, float* y, const float* sigma, int planes, int H, int W, int axis, void* stream);
 /* SimulateLowResolutionTransform: nearest-neighbour down to round(size * zoom[p]), cubic back up; zoom outside (0, 1) copies */
 int du_aug_lowres(const float* x, float* y, const float* zoom, int planes, int H, int W, void* stream);
+/* ---- The same transforms with the interpolation batchgenerators calls (GPUAugment2D(interpolation="spline"), csrc/augment_spline.hip):
+   fp64 arithmetic, one rounding at the store.  Every entry: DU_ERR_BAD_ARG for a NULL pointer or a size < 1, DU_ERR_UNSUPPORTED for a
+   plane of 2^31 elements or more, nothing launched in either case. ---- */
+/* Cubic B-spline coefficients (scipy spline_filter, order 3, mode "mirror") of planes plane_idx[0 .. planes) of x (in_planes, H, W):
+   ws[j] (H, W) fp64 for j < planes; ws holds du_aug_spline_ws_elems(planes, H, W) = 2 planes H W doubles (the second half is the row
+   pass's result).  du_aug_spline_ws_elems launches nothing and returns the (negative) code itself for a bad shape. */
+int64_t du_aug_spline_ws_elems(int planes, int H, int W);
+int du_aug_spline_coeffs(const float* x, int in_planes, const int32_t* plane_idx, int planes, int H, int W, double* ws, int64_t ws_elems,
+                         void* stream);
+/* du_aug_spatial with map_coordinates(order=3, mode="constant", cval=0) for the image: a pixel whose coordinate leaves [0, Hi - 1] x
+   [0, Wi - 1] is 0, inside it is the 4 x 4 B-spline sum over coef (coef_planes, Hi, Wi), slots[b * C + c] naming the plane's coefficients,
+   tap indices mirrored.  Labels: the largest label, -1 included, whose bilinear weight reaches 1/2, else 0: seg_out may hold -1
+   (du_aug_mask).  A sample whose matrix is exactly [1, 0, 0, 1] is the integer centre crop, lower bounds (Hi - Ho) // 2, (Wi - Wo) // 2,
+   of image and labels, flipped; its slots are not read. */
+int du_aug_spatial_spline(const float* data, const float* seg, const float* params, const double* coef, int coef_planes,
+                          const int32_t* slots, float* data_out, float* seg_out, int B, int C, int Hi, int Wi, int Ho, int Wo, void* stream);
+/* du_aug_lowres with skimage's resize going up (scipy zoom(order=3, mode="nearest", grid_mode=True), clipped to the low grid's range).
+   sizes (planes, 2) int32 on the device = the low grid (Hl, Wl) <= (H, W) of every plane, (0, 0) = copy the plane.  Scratch: bounds
+   (planes, 32, 2) fp32 (partial min / max of the low grids), tmp planes H W doubles.  planes <= 65535. */
+int du_aug_lowres_spline(const float* x, float* y, const int32_t* sizes, float* bounds, double* tmp, int planes, int H, int W, void* stream);
+/* MaskTransform + RemoveLabelTransform(-1, 0): where labels (B, 1, n) < 0, the channels c of data (B, C, n) with bit c of channel_bits
+   set become 0 and the label becomes 0.  DU_ERR_BAD_ARG for a bit at or above C (channels 0 .. 62 can be masked). */
+int du_aug_mask(float* data, float* labels, int64_t channel_bits, int B, int C, int64_t n, void* stream);
 
 /* Segmentation head (the decoder's last 1x1 convolution, 32 channels -> K <= 4 classes; dinounet_training.py:603-629, nnU-Net UNetDecoder
    seg_layers): one streaming pass instead of a padded GEMM + layout passes.  bf16 activations, weights rounded to bf16 as autocast does.
