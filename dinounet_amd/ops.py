@@ -2265,6 +2265,7 @@ class _BilinearAdd(torch.autograd.Function):
     def forward(ctx, src, base):
         B, Hs, Ws, Cc, lds = _nhwc(src)
         Bo, Ho, Wo, Co, ldb = _nhwc(base)
+        assert (Bo, Co) == (B, Cc), (tuple(src.shape), tuple(base.shape))     # the kernel takes ONE batch and channel count for both
         out = torch.empty((Bo, Ho, Wo, Co), dtype=base.dtype, device=base.device)
         _lib.check(_lib.lib().du_bilinear_add_fwd(_code(src.dtype), _code(base.dtype), _p(src), lds, _p(base), ldb, _p(out), Co, B, Hs,
                                                   Ws, Ho, Wo, Cc, _st()), "du_bilinear_add_fwd")
