@@ -794,3 +794,463 @@ extern "C" int du_val_dice_bce(const float* logits, const uint8_t* target, float
   hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, R);
   return du_check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Deep supervision (DeepSupervisionWrapper, training/loss/deep_supervision.py, around the three losses above with the weights of
+// nnUNetTrainer._build_loss, nnUNetTrainer.py:373-387): total = sum_s w_s loss_s over the S <= 4 logits tensors of the decoder, largest
+// first, each against the full-resolution label map resampled to its size.  The lower-scale targets of the reference
+// (DownsampleSegForDSTransform2: resize_segmentation(order=0) = skimage resize(order=0, mode="edge", anti_aliasing=False) =
+// scipy.ndimage.zoom(order=0, mode="nearest", grid_mode=True)) are index arithmetic on the full-resolution map,
+//     target_s(y, x) = target(src(y, H / h_s, H), src(x, W / w_s, W)),   src(i, z, n) = floor(clamp((i + 0.5) z - 0.5, 0, n - 1) + 0.5),
+// evaluated in fp64 operation by operation as scipy's NI_ZoomShift does (ds_src_index: the exact value is ((2i + 1) n) div (2 m), but where
+// n / m is not a binary fraction scipy's rounding decides the ties, e.g. 148 -> 18 at i = 13, and the reference's target is scipy's),
+// so they are gathered in the kernels and never stored; region membership is decided from the gathered int64 label and the 64-bit region
+// table (the du_labels_to_regions convention), so no one-hot plane exists at any scale either.  Four launches whatever S is: partial
+// rows (every block serves one scale, found in a by-value descriptor table), one block per scale adding its rows in a fixed order,
+// finish (per-scale losses, total, backward coefficients with w_s folded in), backward of every active scale.  A scale with w_s == 0 is
+// inactive, as in the wrapper: no block is assigned to it, its logits are never read and it gets no gradient.
+// Two per-pixel bodies serve the three label configurations: softmax (plain labels = masked with an ignore value no label takes) and
+// sigmoid regions.  sums (S (2 + 3 C) floats, C = K - 1 or R): [(CE or BCE sum, n_valid) s = 0..S-1 | (I_c, P_c, G_c) c < C, s = 0..S-1]:
+// the Dice slices of all scales are contiguous (sums[2 S:]), one all-reduce covers them under data parallelism.
+namespace {
+
+constexpr int DS_MAX = 4;
+constexpr int64_t DS_NO_IGNORE = INT64_MIN;
+
+struct DsScale {
+  const float* x;       // logits (B, N, h, w) fp32
+  float* dx;            // their gradient (backward launch)
+  int h, w;
+  int first, nblk;      // this scale's blocks: first .. first + nblk - 1 (nblk == 0: inactive)
+  int vec;              // the 4-pixel vector path
+  double zy, zx;        // (double)H / h, (double)W / w: scipy's zoom of the two axes
+};
+struct DsTable {
+  DsScale s[DS_MAX];
+  float wgt[DS_MAX];
+  int S, B, H, W;
+};
+
+// kernel-argument structs are indexed with compile-time indices only (a run-time index would move the table to scratch)
+__device__ __forceinline__ DsScale ds_scale_of_block(const DsTable& d, int& si) {
+  DsScale sc = d.s[0];
+  si = 0;
+#pragma unroll
+  for (int i = 1; i < DS_MAX; i++)
+    if (i < d.S && d.s[i].nblk > 0 && (int)blockIdx.x >= d.s[i].first) { sc = d.s[i]; si = i; }
+  return sc;
+}
+__device__ __forceinline__ float ds_weight(const DsTable& d, int s) {
+  float w = d.wgt[0];
+#pragma unroll
+  for (int i = 1; i < DS_MAX; i++) if (s == i) w = d.wgt[i];
+  return w;
+}
+
+// source index of output position i along an axis of n input and n / zoom output positions: scipy.ndimage.zoom(order=0, mode="nearest",
+// grid_mode=True), NI_ZoomShift's arithmetic step by step in fp64 (no contraction: a fused multiply-add would round differently)
+__device__ __forceinline__ int ds_src_index(int i, double zoom, int n) {
+#pragma clang fp contract(off)
+  double cc = ((double)i + 0.5) * zoom;
+  cc = cc - 0.5;
+  cc = fmin(fmax(cc, 0.0), (double)(n - 1));
+  return (int)floor(cc + 0.5);
+}
+
+// labels of the 4 pixels r0 .. r0 + 3 of image b at a scale of (h, w); tb = target + b H W.  Pixels past the image get `fill`
+// (and are not loaded: their source row would lie past the map)
+__device__ __forceinline__ void ds_labels(const int64_t* __restrict__ tb, long r0, int n, bool full, bool vec, const DsScale& sc, int H, int W,
+                                          int64_t fill, int64_t t[4]) {
+  if (full) { ld4l(tb + r0, vec, n, fill, t); return; }
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    t[j] = fill;
+    if (j < n) {
+      const int r = (int)r0 + j, y = r / sc.w, x = r - y * sc.w;
+      t[j] = tb[(long)ds_src_index(y, sc.zy, H) * W + ds_src_index(x, sc.zx, W)];
+    }
+  }
+}
+
+template <bool SIG, int N>
+__global__ __launch_bounds__(256) void ds_partial_kernel(DsTable d, const int64_t* __restrict__ target, const int64_t* __restrict__ table,
+                                                         float* __restrict__ part, int64_t ignore) {
+  constexpr int CD = SIG ? N : N - 1, NS = 2 + 3 * CD;
+  float acc[NS];
+#pragma unroll
+  for (int i = 0; i < NS; i++) acc[i] = 0.f;
+  int si;
+  const DsScale sc = ds_scale_of_block(d, si);
+  const long HW = (long)sc.h * sc.w, HWf = (long)d.H * d.W;
+  const bool full = sc.h == d.H && sc.w == d.W, vec = sc.vec != 0;
+  const long nq = (HW + 3) >> 2, items = (long)d.B * nq;
+  uint64_t tb[SIG ? N : 1];
+  if constexpr (SIG) {
+#pragma unroll
+    for (int r = 0; r < N; r++) tb[r] = (uint64_t)table[r];
+  }
+  for (long it = (long)((int)blockIdx.x - sc.first) * 256 + threadIdx.x; it < items; it += (long)sc.nblk * 256) {
+    const long b = it / nq, r0 = (it - b * nq) * 4;
+    const int n = vec ? 4 : (int)min(4L, HW - r0);
+    const float* lp = sc.x + b * N * HW + r0;
+    int64_t t[4];
+    ds_labels(target + b * HWf, r0, n, full, vec, sc, d.H, d.W, ignore, t);
+    if constexpr (SIG) {
+      bool m[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) { m[j] = j < n && t[j] != ignore; acc[1] += m[j] ? 1.f : 0.f; }
+#pragma unroll
+      for (int r = 0; r < N; r++) {
+        float x[4];
+        ld4f(lp + (long)r * HW, vec, n, x);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const float y = (t[j] >= 0 && t[j] < 64 && ((tb[r] >> t[j]) & 1ull)) ? 1.f : 0.f;
+          float s, bce;
+          sigmoid_bce(x[j], y, s, bce);
+          acc[0] += m[j] ? bce : 0.f;
+          acc[2 + 3 * r] += m[j] ? s * y : 0.f;
+          acc[2 + 3 * r + 1] += m[j] ? s : 0.f;
+          acc[2 + 3 * r + 2] += m[j] ? y : 0.f;
+        }
+      }
+    } else {
+      float v[N][4];
+#pragma unroll
+      for (int k = 0; k < N; k++) ld4f(lp + (long)k * HW, vec, n, v[k]);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const bool valid = j < n && t[j] != ignore;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < N; k++) mx = fmaxf(mx, v[k][j]);
+        float e[N], se = 0.f, xt = mx;
+#pragma unroll
+        for (int k = 0; k < N; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
+        const float inv = 1.f / se;
+        acc[0] += valid ? (mx + __logf(se)) - xt : 0.f;     // -log p_t = logsumexp - x_t
+        acc[1] += valid ? 1.f : 0.f;
+#pragma unroll
+        for (int k = 1; k < N; k++) {
+          const float pk = e[k] * inv;
+          const bool hit = valid && k == t[j];
+          acc[2 + 3 * (k - 1)] += hit ? pk : 0.f;
+          acc[2 + 3 * (k - 1) + 1] += valid ? pk : 0.f;
+          acc[2 + 3 * (k - 1) + 2] += hit ? 1.f : 0.f;
+        }
+      }
+    }
+  }
+  block_partial_store<NS>(acc, part);      // row blockIdx.x: the rows of one scale are consecutive
+}
+
+// second stage: block s adds the partial rows of scale s (rows t, t + 256, ... per thread, wave tree, waves 0..3: a fixed order) and
+// scatters them into the sums layout above; an inactive scale gets zeros
+template <int CD>
+__global__ __launch_bounds__(256) void ds_rows_sum_kernel(DsTable d, const float* __restrict__ part, float* __restrict__ sums) {
+  constexpr int NS = 2 + 3 * CD;
+  const int s = blockIdx.x;
+  int first = d.s[0].first, nblk = d.s[0].nblk;
+#pragma unroll
+  for (int i = 1; i < DS_MAX; i++) if (s == i) { first = d.s[i].first; nblk = d.s[i].nblk; }
+  float acc[NS];
+#pragma unroll
+  for (int i = 0; i < NS; i++) acc[i] = 0.f;
+  for (int b = threadIdx.x; b < nblk; b += 256) {
+    const float* row = part + (long)(first + b) * NS;
+#pragma unroll
+    for (int i = 0; i < NS; i++) acc[i] += row[i];
+  }
+  __shared__ float red[4][NS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < NS; i++) {
+    const float v = wave_sum(acc[i]);
+    if (lane == 0) red[wave][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    const int i = threadIdx.x;
+    const float v = red[0][i] + red[1][i] + red[2][i] + red[3][i];
+    sums[i < 2 ? 2 * s + i : 2 * d.S + 3 * CD * s + (i - 2)] = v;
+  }
+}
+
+// loss = [total, loss_0 .. loss_{S-1}] (0 for an inactive scale); coef (S, 2 CD + 1) = per scale [(ca_c, cb_c) c < CD, CE / BCE scale],
+// all multiplied by w_s, so the backward pass writes d total / d logits_s.  total = sum of w_s loss_s over the active scales in scale order
+__global__ void ds_finish_kernel(DsTable d, const float* __restrict__ sums, float* __restrict__ loss, float* __restrict__ coef, int CD,
+                                 int sig, int ign, float smooth, float grad_mult) {
+  __shared__ float ls[DS_MAX];
+  const int s = threadIdx.x;
+  if (s < d.S) {
+    const float w = ds_weight(d, s);
+    float* cf = coef + s * (2 * CD + 1);
+    float l = 0.f;
+    if (w != 0.f) {
+      const float dc = dice_coefs(sums + 2 * d.S + 3 * CD * s, cf, CD, smooth, grad_mult * w);
+      const float nv = sums[2 * s + 1];
+      const float scale = nv > 0.f ? 1.f / ((sig && !ign) ? nv * (float)CD : nv) : 0.f;
+      cf[2 * CD] = scale * w;
+      l = sums[2 * s] * scale - dc;
+    } else {
+      for (int i = 0; i < 2 * CD + 1; i++) cf[i] = 0.f;
+    }
+    ls[s] = l;
+    loss[1 + s] = l;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot = 0.f;
+    for (int i = 0; i < d.S; i++) {
+      const float w = ds_weight(d, i);
+      if (w != 0.f) tot += w * ls[i];
+    }
+    loss[0] = tot;
+  }
+}
+
+template <bool SIG, int N>
+__global__ __launch_bounds__(256) void ds_bwd_kernel(DsTable d, const int64_t* __restrict__ target, const int64_t* __restrict__ table,
+                                                     const float* __restrict__ coef, const float* __restrict__ gout, int64_t ignore) {
+  constexpr int CD = SIG ? N : N - 1;
+  int si;
+  const DsScale sc = ds_scale_of_block(d, si);
+  const float* cf = coef + si * (2 * CD + 1);
+  float ca[N], cb[N];
+#pragma unroll
+  for (int c = 0; c < N; c++) {
+    const int q = SIG ? c : c - 1;
+    ca[c] = q >= 0 ? cf[2 * q] : 0.f;
+    cb[c] = q >= 0 ? cf[2 * q + 1] : 0.f;
+  }
+  const float scale = cf[2 * CD];
+  const float go = gout ? gout[0] : 1.f;
+  const long HW = (long)sc.h * sc.w, HWf = (long)d.H * d.W;
+  const bool full = sc.h == d.H && sc.w == d.W, vec = sc.vec != 0;
+  const long nq = (HW + 3) >> 2, items = (long)d.B * nq;
+  uint64_t tb[SIG ? N : 1];
+  if constexpr (SIG) {
+#pragma unroll
+    for (int r = 0; r < N; r++) tb[r] = (uint64_t)table[r];
+  }
+  for (long it = (long)((int)blockIdx.x - sc.first) * 256 + threadIdx.x; it < items; it += (long)sc.nblk * 256) {
+    const long b = it / nq, r0 = (it - b * nq) * 4;
+    const int n = vec ? 4 : (int)min(4L, HW - r0);
+    const float* lp = sc.x + b * N * HW + r0;
+    float* dp = sc.dx + b * N * HW + r0;
+    int64_t t[4];
+    ds_labels(target + b * HWf, r0, n, full, vec, sc, d.H, d.W, ignore, t);
+    if constexpr (SIG) {
+#pragma unroll
+      for (int r = 0; r < N; r++) {
+        float x[4];
+        ld4f(lp + (long)r * HW, vec, n, x);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const bool m = t[j] != ignore;
+          const float y = (t[j] >= 0 && t[j] < 64 && ((tb[r] >> t[j]) & 1ull)) ? 1.f : 0.f;
+          float s, bce;
+          sigmoid_bce(x[j], y, s, bce);
+          x[j] = m ? go * ((s - y) * scale + (ca[r] * y + cb[r]) * s * (1.f - s)) : 0.f;
+        }
+        st4f(dp + (long)r * HW, vec, n, x);
+      }
+    } else {
+      float v[N][4];
+#pragma unroll
+      for (int k = 0; k < N; k++) ld4f(lp + (long)k * HW, vec, n, v[k]);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const bool valid = t[j] != ignore;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < N; k++) mx = fmaxf(mx, v[k][j]);
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < N; k++) { v[k][j] = __expf(v[k][j] - mx); se += v[k][j]; }
+        const float inv = 1.f / se;
+        float g[N], dot = 0.f;
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+          v[k][j] *= inv;
+          g[k] = (k == t[j] ? ca[k] : 0.f) + cb[k];
+          dot += g[k] * v[k][j];
+        }
+#pragma unroll
+        for (int k = 0; k < N; k++)
+          v[k][j] = valid ? go * ((v[k][j] - (k == t[j] ? 1.f : 0.f)) * scale + v[k][j] * (g[k] - dot)) : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < N; k++) st4f(dp + (long)k * HW, vec, n, v[k]);
+    }
+  }
+}
+
+// DownsampleSegForDSTransform2 on the device: every requested map in one launch, one output pixel per lane
+struct DsSegTable {
+  int64_t* out[DS_MAX];
+  int h[DS_MAX], w[DS_MAX];
+  double zy[DS_MAX], zx[DS_MAX];
+  long end[DS_MAX];      // exclusive end of map s in the concatenated output index space (B h w pixels each)
+  int S, H, W;
+};
+__global__ __launch_bounds__(256) void ds_downsample_seg_kernel(DsSegTable d, const int64_t* __restrict__ seg) {
+  const long total = d.end[DS_MAX - 1];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    int64_t* out = d.out[0];
+    int h = d.h[0], w = d.w[0];
+    double zy = d.zy[0], zx = d.zx[0];
+    long base = 0;
+#pragma unroll
+    for (int s = 1; s < DS_MAX; s++)
+      if (i >= d.end[s - 1]) { out = d.out[s]; h = d.h[s]; w = d.w[s]; zy = d.zy[s]; zx = d.zx[s]; base = d.end[s - 1]; }
+    const long li = i - base, hw = (long)h * w;
+    const long b = li / hw;
+    const int r = (int)(li - b * hw), y = r / w, x = r - y * w;
+    out[li] = seg[b * (long)d.H * d.W + (long)ds_src_index(y, zy, d.H) * d.W + ds_src_index(x, zx, d.W)];
+  }
+}
+
+// host side of the descriptor table.  bwd: the backward launch's grids and the gradient pointers.  Returns 0 or a DU_ERR_*
+int ds_table(DsTable& d, const float* const* logits, float* const* dlogits, const void* target, int B, int H, int W, int S, const int* hs,
+             const int* wd, const float* weights, bool bwd, int& total) {
+  total = 0;
+  if (S < 1 || !hs || !wd || !weights || B <= 0 || H <= 0 || W <= 0) return DU_ERR_BAD_ARG;
+  if (S > DS_MAX || H > 32768 || W > 32768) return DU_ERR_UNSUPPORTED;       // pixel indices of a map in 32 bits
+  d.S = S; d.B = B; d.H = H; d.W = W;
+  bool any = false;
+  for (int s = 0; s < DS_MAX; s++) {
+    DsScale& sc = d.s[s];
+    sc = DsScale{nullptr, nullptr, 1, 1, 0, 0, 0, 1.0, 1.0};
+    d.wgt[s] = 0.f;
+    if (s >= S) continue;
+    if (hs[s] <= 0 || wd[s] <= 0 || hs[s] > H || wd[s] > W) return DU_ERR_BAD_ARG;      // a scale larger than the target
+    sc.h = hs[s]; sc.w = wd[s];
+    sc.zy = (double)H / (double)sc.h; sc.zx = (double)W / (double)sc.w;
+    if (!(weights[s] == weights[s])) return DU_ERR_BAD_ARG;
+    d.wgt[s] = weights[s];
+    if (weights[s] == 0.f) continue;
+    any = true;
+    if (logits) {
+      if (!logits[s] || (bwd && (!dlogits || !dlogits[s]))) return DU_ERR_BAD_ARG;
+      sc.x = logits[s];
+      sc.dx = bwd ? dlogits[s] : nullptr;
+    }
+    const int64_t HW = (int64_t)sc.h * sc.w;
+    const long items = quad_items(B, HW);
+    if (items >= (1L << 31)) return DU_ERR_UNSUPPORTED;
+    const bool full = sc.h == H && sc.w == W;
+    sc.vec = HW % 4 == 0 && al(sc.x, 16) && (!bwd || al(sc.dx, 16)) && (!full || al(target, 16));
+    sc.first = total;
+    sc.nblk = bwd ? elem_grid(items) : masked_grid(items);
+    total += sc.nblk;
+  }
+  return any ? 0 : DU_ERR_BAD_ARG;         // the wrapper asserts at least one weight != 0
+}
+
+// mode 0: softmax over C = K classes (2..8), mode 1: sigmoid over C = R regions (1..8)
+int ds_mode_ok(int mode, int C) {
+  if (mode != 0 && mode != 1) return DU_ERR_BAD_ARG;
+  if (mode == 0 ? (C < 2 || C > 8) : (C < 1 || C > MAXR)) return DU_ERR_UNSUPPORTED;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t du_ds_loss_ws_elems(int mode, int B, int C, int H, int W, int S, const int* hs, const int* wd, const float* weights) {
+  if (ds_mode_ok(mode, C) != 0) return 0;
+  DsTable d;
+  int total;
+  if (ds_table(d, nullptr, nullptr, nullptr, B, H, W, S, hs, wd, weights, false, total) != 0) return 0;
+  return (int64_t)total * (2 + 3 * (mode == 0 ? C - 1 : C));
+}
+
+extern "C" int du_ds_loss_sums(int mode, const float* const* logits, const int64_t* target, const int64_t* table, float* sums, int B, int C,
+                               int H, int W, int S, const int* hs, const int* wd, const float* weights, int has_ignore,
+                               int64_t ignore_label, float* ws, int64_t ws_elems, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !target || !sums || !ws || (has_ignore != 0 && has_ignore != 1) || (mode == 1 && !table)) return DU_ERR_BAD_ARG;
+  if (int rc = ds_mode_ok(mode, C)) return rc;
+  DsTable d;
+  int total;
+  if (int rc = ds_table(d, logits, nullptr, target, B, H, W, S, hs, wd, weights, false, total)) return rc;
+  const int CD = mode == 0 ? C - 1 : C;
+  if (ws_elems < (int64_t)total * (2 + 3 * CD)) return DU_ERR_BAD_ARG;
+  const int64_t ignore = has_ignore ? ignore_label : DS_NO_IGNORE;
+  if (mode == 0) {
+#define CALL(KK) hipLaunchKernelGGL((ds_partial_kernel<false, KK>), dim3(total), dim3(256), 0, st, d, target, table, ws, ignore); \
+                 hipLaunchKernelGGL(ds_rows_sum_kernel<KK - 1>, dim3(S), dim3(256), 0, st, d, (const float*)ws, sums)
+    LOSS_K_SWITCH(C, CALL)
+#undef CALL
+  } else {
+#define CALL(RR) hipLaunchKernelGGL((ds_partial_kernel<true, RR>), dim3(total), dim3(256), 0, st, d, target, table, ws, ignore); \
+                 hipLaunchKernelGGL(ds_rows_sum_kernel<RR>, dim3(S), dim3(256), 0, st, d, (const float*)ws, sums)
+    LOSS_R_SWITCH(C, CALL)
+#undef CALL
+  }
+  return du_check_launch();
+}
+
+extern "C" int du_ds_loss_finish(int mode, const float* sums, float* loss, float* coef, int C, int S, const float* weights, int has_ignore,
+                                 float smooth, float grad_mult, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!sums || !loss || !coef || !weights || S < 1 || (has_ignore != 0 && has_ignore != 1)) return DU_ERR_BAD_ARG;
+  if (S > DS_MAX) return DU_ERR_UNSUPPORTED;
+  if (int rc = ds_mode_ok(mode, C)) return rc;
+  DsTable d;
+  d.S = S; d.B = 0; d.H = 0; d.W = 0;
+  bool any = false;
+  for (int s = 0; s < DS_MAX; s++) {
+    d.s[s] = DsScale{nullptr, nullptr, 1, 1, 0, 0, 0, 1.0, 1.0};
+    d.wgt[s] = s < S ? weights[s] : 0.f;
+    any = any || d.wgt[s] != 0.f;
+  }
+  if (!any) return DU_ERR_BAD_ARG;
+  hipLaunchKernelGGL(ds_finish_kernel, dim3(1), dim3(64), 0, st, d, sums, loss, coef, mode == 0 ? C - 1 : C, mode, has_ignore, smooth,
+                     grad_mult);
+  return du_check_launch();
+}
+
+extern "C" int du_ds_loss_bwd(int mode, const float* const* logits, const int64_t* target, const int64_t* table, const float* coef,
+                              const float* grad_out, float* const* dlogits, int B, int C, int H, int W, int S, const int* hs, const int* wd,
+                              const float* weights, int has_ignore, int64_t ignore_label, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!logits || !dlogits || !target || !coef || (has_ignore != 0 && has_ignore != 1) || (mode == 1 && !table)) return DU_ERR_BAD_ARG;
+  if (int rc = ds_mode_ok(mode, C)) return rc;
+  DsTable d;
+  int total;
+  if (int rc = ds_table(d, logits, dlogits, target, B, H, W, S, hs, wd, weights, true, total)) return rc;
+  const int64_t ignore = has_ignore ? ignore_label : DS_NO_IGNORE;
+  if (mode == 0) {
+#define CALL(KK) hipLaunchKernelGGL((ds_bwd_kernel<false, KK>), dim3(total), dim3(256), 0, st, d, target, table, coef, grad_out, ignore)
+    LOSS_K_SWITCH(C, CALL)
+#undef CALL
+  } else {
+#define CALL(RR) hipLaunchKernelGGL((ds_bwd_kernel<true, RR>), dim3(total), dim3(256), 0, st, d, target, table, coef, grad_out, ignore)
+    LOSS_R_SWITCH(C, CALL)
+#undef CALL
+  }
+  return du_check_launch();
+}
+
+extern "C" int du_downsample_seg(const int64_t* seg, int64_t* const* outs, int B, int H, int W, int S, const int* hs, const int* wd,
+                                 void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!seg || !outs || !hs || !wd || B <= 0 || H <= 0 || W <= 0 || S < 1) return DU_ERR_BAD_ARG;
+  if (S > DS_MAX || H > 32768 || W > 32768) return DU_ERR_UNSUPPORTED;
+  DsSegTable d;
+  d.S = S; d.H = H; d.W = W;
+  long end = 0;
+  for (int s = 0; s < DS_MAX; s++) {
+    d.out[s] = nullptr; d.h[s] = 1; d.w[s] = 1; d.zy[s] = 1.0; d.zx[s] = 1.0;
+    if (s < S) {
+      if (!outs[s] || hs[s] <= 0 || wd[s] <= 0 || hs[s] > H || wd[s] > W) return DU_ERR_BAD_ARG;
+      d.out[s] = outs[s]; d.h[s] = hs[s]; d.w[s] = wd[s];
+      d.zy[s] = (double)H / (double)hs[s]; d.zx[s] = (double)W / (double)wd[s];
+      end += (long)B * hs[s] * wd[s];
+    }
+    d.end[s] = end;
+  }
+  hipLaunchKernelGGL(ds_downsample_seg_kernel, dim3(elem_grid(end)), dim3(256), 0, st, d, seg);
+  return du_check_launch();
+}

@@ -487,3 +487,35 @@ class TrainBatches:
             target = labels_to_regions(target, self.regions, self.ignore_label, table=self.table)
         self.last_draw = (d, a)
         return x, target
+
+
+def downsample_seg_for_ds(seg, shapes_or_scales):
+    """DownsampleSegForDSTransform2 (data_augmentation/custom_transforms/deep_supervision_donwsampling.py, the last training transform,
+    nnUNetTrainer.py:770-771; order 0): seg (B,C,H,W) integer labels -> the reference's list, one map per entry.  An entry is a shape
+    (h, w) of ints, or a scale: a float or one float per axis (deep_supervision_scales), giving round(H s), round(W s) as np.round does.
+    An entry that keeps the size returns `seg` itself, as the reference does.  The maps are resize_segmentation(order=0) of seg, which is
+    scipy.ndimage.zoom(order=0, mode="nearest", grid_mode=True): the source indices are training.ds_target_index per axis.  On the GPU
+    one launch writes up to four maps (du_downsample_seg); on the CPU torch indexing.  DeepSupervisionLoss needs none of this: it
+    resamples the full-resolution target inside its kernels."""
+    from .training import downsample_target
+    if seg.dim() != 4:
+        raise ValueError(f"downsample_seg_for_ds: seg must be (B,C,H,W), got {tuple(seg.shape)}")
+    H, W = int(seg.shape[2]), int(seg.shape[3])
+    shapes = []
+    for e in shapes_or_scales:
+        e = list(e) if isinstance(e, (tuple, list)) else [e, e]
+        if len(e) != 2:
+            raise ValueError(f"downsample_seg_for_ds: entry {e!r} is neither a (h, w) shape nor one scale per axis")
+        if all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in e):
+            h, w = int(e[0]), int(e[1])
+        else:
+            h, w = int(round(H * float(e[0]))), int(round(W * float(e[1])))
+        if not (1 <= h <= H and 1 <= w <= W):
+            raise ValueError(f"downsample_seg_for_ds: entry {e!r} gives {(h, w)}, outside 1..{(H, W)}")
+        shapes.append((h, w))
+    small = [s for s in shapes if s != (H, W)]
+    if seg.is_cuda and small:
+        from . import ops
+        made = iter(o if o.dtype == seg.dtype else o.to(seg.dtype) for o in ops.downsample_seg(seg, small))   # the kernel works in int64
+        return [seg if s == (H, W) else next(made) for s in shapes]
+    return [downsample_target(seg, s) for s in shapes]

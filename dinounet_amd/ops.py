@@ -20,7 +20,7 @@ from ._lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SWIGLU, DU_BF16,
 
 __all__ = ["mm", "linear", "conv2d", "conv_transpose2x2", "norm_act", "layer_norm", "msda", "dwconv3x3",
            "maxpool3x3s2", "bilinear_add", "bilinear_resize", "squeeze_excite", "dice_ce_loss", "dice_ce_masked_loss", "dice_bce_loss",
-           "labels_to_regions", "val_dice_ce", "val_dice_bce"]
+           "labels_to_regions", "val_dice_ce", "val_dice_bce", "ds_seg_loss", "downsample_seg"]
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -2523,6 +2523,113 @@ def labels_to_regions(seg, table, ignore_label=None):
     _lib.check(_lib.lib().du_labels_to_regions(_p(s), _p(table.contiguous()), _p(out), B, R, H * W, u,
                                                0 if ignore_label is None else int(ignore_label), _st()), "du_labels_to_regions")
     return out
+
+
+class _DSSegLoss(torch.autograd.Function):
+    """DeepSupervisionWrapper (training/loss/deep_supervision.py) around DC_and_CE_loss / DC_and_BCE_loss on the list of fp32 NCHW logits
+    of a deep-supervision decoder, fused over the scales (csrc/loss.hip, du_ds_loss_*): the lower-scale targets are gathered from the
+    full-resolution label map inside the kernels.  Four launches whatever the number of scales: du_ds_loss_sums (2), du_ds_loss_finish
+    (1) in forward, du_ds_loss_bwd (1) in backward.  A zero-weight scale is never read and gets a None gradient."""
+
+    @staticmethod
+    def forward(ctx, target, mode, weights, table, ignore_label, smooth, group, *outs):
+        S = len(outs)
+        B, Cn = outs[0].shape[0], outs[0].shape[1]
+        H, W = target.shape[-2], target.shape[-1]
+        tgt = target.reshape(B, H * W)
+        if tgt.dtype != torch.int64:
+            tgt = tgt.long()
+        tgt = tgt.contiguous()
+        dev = tgt.device
+        xs = [o.float().contiguous() if w != 0.0 else None for o, w in zip(outs, weights)]
+        hs = (C.c_int * S)(*[int(o.shape[2]) for o in outs])
+        wd = (C.c_int * S)(*[int(o.shape[3]) for o in outs])
+        wt = (C.c_float * S)(*[float(w) for w in weights])
+        ptrs = (C.c_void_p * S)(*[None if x is None else x.data_ptr() for x in xs])
+        m = 1 if mode == "regions" else 0
+        u = 0 if ignore_label is None else 1
+        ig = 0 if ignore_label is None else int(ignore_label)
+        CD = Cn if m else Cn - 1
+        L = _lib.lib()
+        n = int(L.du_ds_loss_ws_elems(m, B, Cn, H, W, S, hs, wd, wt))
+        if n <= 0:
+            raise RuntimeError(f"dinounet_hip: the fused deep-supervision loss supports 1..4 scales no larger than the target, 2..8 classes "
+                               f"or 1..8 regions and at least one non-zero weight; got {S} scales {[tuple(o.shape) for o in outs]}, "
+                               f"target {(H, W)}, weights {list(weights)}")
+        ws = torch.empty(n, dtype=torch.float32, device=dev)
+        sums = torch.empty(S * (2 + 3 * CD), dtype=torch.float32, device=dev)
+        _lib.check(L.du_ds_loss_sums(m, ptrs, _p(tgt), _p(table), _p(sums), B, Cn, H, W, S, hs, wd, wt, u, ig, _p(ws), n, _st()),
+                   "du_ds_loss_sums")
+        mult = 1.0
+        if group is not None and torch.distributed.is_initialized():
+            _small_all_reduce(sums[2 * S:], group, "dice_sums")           # the Dice slices of every scale in one collective
+            mult = float(torch.distributed.get_world_size(group))
+        loss = torch.empty(1 + S, dtype=torch.float32, device=dev)
+        coef = torch.empty(S * (2 * CD + 1), dtype=torch.float32, device=dev)
+        _lib.check(L.du_ds_loss_finish(m, _p(sums), _p(loss), _p(coef), Cn, S, wt, u, float(smooth), mult, _st()), "du_ds_loss_finish")
+        ctx.save_for_backward(tgt, coef, table, *[x for x in xs if x is not None])
+        ctx.cfg = (m, u, ig, S, B, Cn, H, W, [float(w) for w in weights], [tuple(o.shape) for o in outs], table is not None)
+        losses = loss[1:]
+        ctx.mark_non_differentiable(losses)
+        return loss[0], losses
+
+    @staticmethod
+    def backward(ctx, go, _unused):
+        m, u, ig, S, B, Cn, H, W, weights, shapes, has_table = ctx.cfg
+        tgt, coef, table = ctx.saved_tensors[:3]
+        act = list(ctx.saved_tensors[3:])
+        xs = [act.pop(0) if w != 0.0 else None for w in weights]
+        dls = [None if x is None else torch.empty_like(x) for x in xs]
+        hs = (C.c_int * S)(*[sh[2] for sh in shapes])
+        wd = (C.c_int * S)(*[sh[3] for sh in shapes])
+        wt = (C.c_float * S)(*weights)
+        ptrs = (C.c_void_p * S)(*[None if x is None else x.data_ptr() for x in xs])
+        dptrs = (C.c_void_p * S)(*[None if x is None else x.data_ptr() for x in dls])
+        gof = go.float().contiguous()
+        _lib.check(_lib.lib().du_ds_loss_bwd(m, ptrs, _p(tgt), _p(table) if has_table else None, _p(coef), _p(gof), dptrs, B, Cn, H, W, S,
+                                             hs, wd, wt, u, ig, _st()), "du_ds_loss_bwd")
+        return (None,) * 7 + tuple(dls)
+
+
+def ds_seg_loss(outs, target, mode, weights, table=None, ignore_label=None, smooth=1e-5, group=None, return_scale_losses=False):
+    """outs: list of fp32 (B,C,h_s,w_s) logits, largest first (1..4), outs[0] at the target's size; target (B,1,H,W) integer labels at
+    full resolution; mode "softmax" | "softmax_ignore" | "regions" (table: the (R) int64 device bit masks of build_loss); weights: one
+    float per scale.  -> total = sum_s w_s loss_s (scalar); with return_scale_losses also the (S) per-scale losses (0 where w_s == 0)."""
+    if isinstance(target, (list, tuple)):
+        raise ValueError("ds_seg_loss: pass the full-resolution target (the first element of the reference's list); the lower scales "
+                         "are resampled from it")
+    outs = list(outs)
+    _req(target, table, *outs)
+    if len(weights) != len(outs):
+        raise ValueError(f"ds_seg_loss: {len(outs)} outputs, {len(weights)} weights")
+    if tuple(outs[0].shape[-2:]) != tuple(target.shape[-2:]):
+        raise ValueError(f"ds_seg_loss: outs[0] is {tuple(outs[0].shape[-2:])}, the target {tuple(target.shape[-2:])}")
+    if mode == "regions" and table is None:
+        raise ValueError("ds_seg_loss: region mode needs the region table")
+    if mode != "regions":
+        table = None
+    if mode == "softmax":
+        ignore_label = None
+    weights = tuple(C.c_float(float(w)).value for w in weights)       # as the kernels see them: a weight that rounds to 0 is inactive
+    total, losses = _DSSegLoss.apply(target, mode, weights, table, ignore_label, smooth, group, *outs)
+    return (total, losses) if return_scale_losses else total
+
+
+def downsample_seg(seg, shapes):
+    """DownsampleSegForDSTransform2 on the device: seg (B,C,H,W) integer labels -> [ (B,C,h,w) int64 for (h, w) in shapes ], one launch
+    per four maps (du_downsample_seg; scipy.ndimage.zoom(order=0, mode="nearest", grid_mode=True) as index arithmetic)."""
+    _req(seg)
+    B, Cn, H, W = seg.shape
+    s = seg if seg.dtype == torch.int64 else seg.long()
+    s = s.contiguous()
+    outs = [torch.empty((B, Cn, int(h), int(w)), dtype=torch.int64, device=seg.device) for h, w in shapes]
+    for i in range(0, len(outs), 4):
+        grp = outs[i:i + 4]
+        n = len(grp)
+        _lib.check(_lib.lib().du_downsample_seg(_p(s), (C.c_void_p * n)(*[o.data_ptr() for o in grp]), B * Cn, H, W, n,
+                                                (C.c_int * n)(*[o.shape[2] for o in grp]), (C.c_int * n)(*[o.shape[3] for o in grp]),
+                                                _st()), "du_downsample_seg")
+    return outs
 
 
 def _val_bufs(C_, counts, accum, device):

@@ -2,7 +2,8 @@
 (dinounet/training/nnUNetTrainer/nnUNetTrainer.py:899-929): forward -> DC+CE loss -> backward -> clip_grad_norm_(12)
 -> SGD(nesterov, momentum 0.99, wd 3e-5).  On the GPU the loss is the fused Dice+CE kernel pair (csrc/loss.hip) and clip + SGD the
 fused three-launch optimiser (csrc/optim.hip); the torch formula below serves the CPU / many-class path of the gloo tests.
-build_loss covers the trainer's other label configurations (ignore label, regions: nnUNetTrainer.py:355-365); ValStep / validation_counts
+build_loss covers the trainer's other label configurations (ignore label, regions: nnUNetTrainer.py:355-365) and, with
+deep_supervision_weights, the DeepSupervisionWrapper around them (DeepSupervisionLoss: one fused multi-scale pass); ValStep / validation_counts
 are the validation half of the epoch (validation_step / on_validation_epoch_end, nnUNetTrainer.py:946-1052)."""
 import os
 import threading
@@ -182,7 +183,8 @@ def labels_to_regions(seg, regions, ignore_label=None, table=None):
 
 
 class SegLoss(torch.nn.Module):
-    """What nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365) returns for 2D, no deep supervision, batch Dice: DC_and_CE_loss (plain
+    """What nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365) returns for 2D, batch Dice, before the deep-supervision wrapper
+    (DeepSupervisionLoss below adds it): DC_and_CE_loss (plain
     labels or with an ignore label) or DC_and_BCE_loss (regions, with or without an ignore label).  Called as loss(logits, target) with
     integer label maps (B,1,H,W) in both modes; in region mode the labels become the one-hot region target on the device inside the same
     step (labels_to_regions with the table built here, at construction, outside any capture)."""
@@ -218,12 +220,138 @@ class SegLoss(torch.nn.Module):
         return dc_and_bce_loss(logits, onehot, self.ignore_label is not None, self.smooth, ddp=self.ddp, group=self.group)
 
 
-def build_loss(num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None):
-    """nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365) for this package: the loss module for plain labels, labels with an ignore
+def deep_supervision_scales(pool_op_kernel_sizes):
+    """nnUNetTrainer._get_deep_supervision_scales (nnUNetTrainer.py:300-306): 1 / cumprod of the pooling kernel sizes along the stages,
+    the last (lowest) stage dropped -> one list of per-axis scales per deep-supervision output, largest first ([1.0, 1.0] first)."""
+    out, cp = [], None
+    for k in pool_op_kernel_sizes:
+        k = [k] if isinstance(k, (int, float)) else list(k)
+        cp = [float(v) for v in k] if cp is None else [a * float(v) for a, v in zip(cp, k)]
+        out.append([1.0 / v for v in cp])
+    return out[:-1]
+
+
+def deep_supervision_weights(n_outputs, ddp=False):
+    """the weights of nnUNetTrainer._build_loss (nnUNetTrainer.py:373-387): 1 / 2**i per output, the last set to 0 -- or to 1e-6 under
+    DDP, the reference's workaround for DDP's unused-parameter check -- then divided by their sum.  Three outputs: [2/3, 1/3, 0]."""
+    if isinstance(n_outputs, bool) or not isinstance(n_outputs, int) or n_outputs < 1:
+        raise ValueError(f"deep_supervision_weights: n_outputs must be a positive int, got {n_outputs!r}")
+    w = [1.0 / (2 ** i) for i in range(n_outputs)]
+    w[-1] = 1e-6 if ddp else 0.0
+    tot = sum(w)
+    if tot == 0.0:
+        raise ValueError("deep_supervision_weights: a single output without DDP leaves no non-zero weight")
+    return [v / tot for v in w]
+
+
+def ds_target_index(n_out, n_in, device=None):
+    """source index of every output position of resize_segmentation(order=0) along one axis, i.e. what scipy.ndimage.zoom(order=0,
+    mode="nearest", grid_mode=True) (= skimage resize(order=0, mode="edge", anti_aliasing=False)) picks:
+    floor(clamp((i + 0.5) z - 0.5, 0, n_in - 1) + 0.5) with z = n_in / n_out, evaluated in float64 step by step as scipy's NI_ZoomShift
+    does.  In exact arithmetic that is ((2 i + 1) n_in) div (2 n_out) (round half up); the two differ only where z is not a binary
+    fraction and the exact coordinate is a tie, which scipy's rounding then decides (148 -> 18 at i = 13: 110, not 111) -- and the
+    reference's targets are scipy's.  The identity for n_out == n_in."""
+    z = float(n_in) / float(n_out)
+    cc = (torch.arange(n_out, dtype=torch.float64, device=device) + 0.5) * z
+    cc = (cc - 0.5).clamp(0.0, float(n_in - 1))
+    return torch.floor(cc + 0.5).to(torch.int64)
+
+
+def downsample_target(target, hw):
+    """target (B,C,H,W) -> (B,C,h,w) by the index formula of ds_target_index (DownsampleSegForDSTransform2, order 0); torch indexing"""
+    H, W = target.shape[-2], target.shape[-1]
+    h, w = int(hw[0]), int(hw[1])
+    if (h, w) == (H, W):
+        return target
+    return target[:, :, ds_target_index(h, H, target.device)][:, :, :, ds_target_index(w, W, target.device)]
+
+
+class DeepSupervisionLoss(torch.nn.Module):
+    """DeepSupervisionWrapper (training/loss/deep_supervision.py) around a SegLoss, as nnUNetTrainer._build_loss wraps it
+    (nnUNetTrainer.py:373-387): loss(outs, target) = sum_s w_s base(outs[s], target_s) over the scales with w_s != 0, in scale order; a
+    zero-weight output is not read and gets no gradient.  outs: the list a deep-supervision decoder returns, largest first.  target: the
+    full-resolution label map (B,1,H,W) alone -- the reference's target list is DownsampleSegForDSTransform2 of its first element
+    (order 0, the last transform), so target_s is resampled from it here (ds_target_index); a list raises ValueError.
+    On the GPU within the class limits of the fused losses: one fused multi-scale pass (ops.ds_seg_loss, four launches whatever the
+    number of scales, no target pyramid in memory).  Otherwise (CPU, more classes): the composition of the per-scale losses on indexed
+    targets, which is also the fp64 oracle of the GPU tests.  mode, regions, ignore_label, smooth, ddp, group and table are the base's."""
+
+    MAX_FUSED_SCALES = 4
+
+    def __init__(self, base, weights):
+        super().__init__()
+        if not isinstance(base, SegLoss):
+            raise TypeError(f"DeepSupervisionLoss wraps a SegLoss (build_loss), got {type(base).__name__}")
+        weights = tuple(float(w) for w in weights)
+        if not weights or not any(w != 0.0 for w in weights):
+            raise ValueError("DeepSupervisionLoss: at least one weight must be != 0")
+        self.base, self.weights = base, weights
+
+    mode = property(lambda self: self.base.mode)
+    regions = property(lambda self: self.base.regions)
+    ignore_label = property(lambda self: self.base.ignore_label)
+    smooth = property(lambda self: self.base.smooth)
+    ddp = property(lambda self: self.base.ddp)
+    group = property(lambda self: self.base.group)
+    num_classes = property(lambda self: self.base.num_classes)
+    table = property(lambda self: getattr(self.base, "table", None))
+
+    def _check(self, outs, target):
+        if isinstance(target, (list, tuple)):
+            raise ValueError("DeepSupervisionLoss: pass the full-resolution target, i.e. the first element of the reference's target "
+                             "list; the lower scales are resampled from it")
+        if not isinstance(outs, (list, tuple)):
+            raise TypeError("DeepSupervisionLoss: the network output must be a list of logits (a decoder with deep_supervision=True)")
+        if len(outs) != len(self.weights):
+            raise ValueError(f"DeepSupervisionLoss: {len(outs)} outputs, {len(self.weights)} weights")
+        if tuple(outs[0].shape[-2:]) != tuple(target.shape[-2:]):
+            raise ValueError(f"DeepSupervisionLoss: outs[0] is {tuple(outs[0].shape[-2:])}, the target {tuple(target.shape[-2:])}")
+
+    def fused(self, outs):
+        C_ = outs[0].shape[1]
+        return (all(o.is_cuda for o in outs) and len(outs) <= self.MAX_FUSED_SCALES
+                and ((1 <= C_ <= 8) if self.mode == "regions" else (2 <= C_ <= 8)))
+
+    def composed(self, outs, target):
+        """the torch formula: the pyramid by integer indexing, the base loss per scale, the weighted sum"""
+        self._check(outs, target)
+        total = None
+        for w, o in zip(self.weights, outs):
+            if w == 0.0:
+                continue
+            l = w * self.base(o, downsample_target(target, o.shape[-2:]))
+            total = l if total is None else total + l
+        return total
+
+    def forward(self, outs, target, return_scale_losses=False):
+        self._check(outs, target)
+        if not self.fused(outs):
+            if return_scale_losses:
+                raise RuntimeError("DeepSupervisionLoss: per-scale losses come from the fused pass only")
+            return self.composed(outs, target)
+        from . import ops
+        ddp = self.ddp if self.ddp is not None else _ddp_default(self.group)
+        table = None
+        if self.mode == "regions":
+            table = self.table
+            if table.device != target.device:
+                raise RuntimeError(f"DeepSupervisionLoss: region table lives on {table.device}, target on {target.device} "
+                                   "(move the module with .to())")
+        return ops.ds_seg_loss(outs, target, self.mode, self.weights, table=table, ignore_label=self.ignore_label, smooth=self.smooth,
+                               group=(self.group if self.group is not None else dist.group.WORLD) if ddp else None,
+                               return_scale_losses=return_scale_losses)
+
+
+def build_loss(num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None, deep_supervision_weights=None):
+    """nnUNetTrainer._build_loss (nnUNetTrainer.py:355-387) for this package: the loss module for plain labels, labels with an ignore
     label, or regions (each an int or a tuple of ints; num_classes = number of network outputs = len(regions)).  Validated on the host:
     ValueError for an ignore label below num_classes, more than 8 regions, a region label outside 0..63 or an ignore label inside a
-    region.  Pass the result to TrainStep(loss=...)."""
-    return SegLoss(num_classes, regions=regions, ignore_label=ignore_label, smooth=smooth, ddp=ddp, group=group)
+    region.  With `deep_supervision_weights` (one per decoder output, e.g. deep_supervision_weights(3)) the module is wrapped in a
+    DeepSupervisionLoss, called as loss(outs, target) on the decoder's list.  Pass the result to TrainStep(loss=...)."""
+    base = SegLoss(num_classes, regions=regions, ignore_label=ignore_label, smooth=smooth, ddp=ddp, group=group)
+    if deep_supervision_weights is None:
+        return base
+    return DeepSupervisionLoss(base, deep_supervision_weights)
 
 
 class _CaptureSegments:
@@ -297,6 +425,7 @@ class TrainStep:
         self.net, self.opt, self.params, self.reducer, self.max_norm = net, optimizer, params, reducer, max_norm
         self.ddp_loss = ddp_loss         # None: batch-Dice sums all-reduced iff world size > 1 (dice.py:58-119 with ddp=True)
         self.loss_fn = loss              # None: dc_and_ce_loss on plain labels; else a build_loss module, called as loss(logits, tgt)
+        #                                  (a DeepSupervisionLoss for a network that returns the deep-supervision list)
         if comm_outside_graph is None:
             comm_outside_graph = os.environ.get("DINOUNET_COMM_OUTSIDE_GRAPH", "0") == "1"
         self.comm_outside_graph = bool(comm_outside_graph) and reducer is not None
@@ -315,7 +444,15 @@ class TrainStep:
     def _step(self):
         self.opt.zero_grad(set_to_none=True)
         logits = self.net(self.x)
-        if self.loss_fn is None:
+        if isinstance(logits, (list, tuple)):
+            # a deep-supervision decoder: the list goes to a DeepSupervisionLoss with the one full-resolution target buffer
+            if not isinstance(self.loss_fn, DeepSupervisionLoss):
+                raise TypeError("TrainStep: the network returns a list of logits (deep supervision) but the loss is "
+                                f"{'the default dc_and_ce_loss' if self.loss_fn is None else type(self.loss_fn).__name__}; pass "
+                                "loss=build_loss(..., deep_supervision_weights=deep_supervision_weights(n_outputs))")
+            loss = self.loss_fn(logits, self.tgt)
+            logits = logits[0]
+        elif self.loss_fn is None:
             loss = dc_and_ce_loss(logits, self.tgt, ddp=self.ddp_loss)
         else:
             loss = self.loss_fn(logits, self.tgt)
@@ -567,6 +704,8 @@ class ValStep:
     and running statistics in place, so it stays valid while a TrainStep on the same `net` updates them (not if they are re-allocated:
     build a new ValStep then; inference.clear_window_cache states the same rule).  `loss`: a build_loss module or None (plain labels);
     mode, regions, ignore label, smooth, ddp and group come from it, the region table was built with it, outside any capture.  With a
+    DeepSupervisionLoss and a network that returns a list, the step loss is the module's multi-scale forward value (validation_step :963)
+    while the counts come from outs[0] and the full-resolution target (:966-968); with any other loss a list is reduced to outs[0].  With a
     group the Dice sums are all-reduced as in the training forward (the reference's validation loss is the same module); under a
     capture that all-reduce is recorded into the graph, a capture that fails falls back to eager steps with a warning, and the multi-rank
     capture itself has been run on CPU / gloo eager steps only, not on several GPUs."""
@@ -580,6 +719,7 @@ class ValStep:
         self.smooth = 1e-5 if loss is None else loss.smooth
         self.ddp = None if loss is None else loss.ddp
         self.group = None if loss is None else loss.group
+        self.ds_loss = loss if isinstance(loss, DeepSupervisionLoss) else None      # step loss = its multi-scale forward value
         self.table = None
         if self.regions is not None and device.type == "cuda":
             self.table = loss.table if loss.table.device == device else _region_table(self.regions, device)
@@ -601,7 +741,10 @@ class ValStep:
         try:
             with torch.no_grad():
                 logits = self.net(self.x)
+                ds_loss = None
                 if isinstance(logits, (list, tuple)):
+                    if self.ds_loss is not None:     # validation_step :963: the loss module on the whole list; counts from outs[0] (:966-968)
+                        ds_loss = self.ds_loss(logits, self.tgt).detach()
                     logits = logits[0]
                 if self.counts is None:
                     C_ = logits.shape[1]
@@ -609,6 +752,8 @@ class ValStep:
                     self.step_counts = torch.zeros((3, C_), dtype=torch.int64, device=self.x.device)
                 loss, _ = _val_loss_counts(logits, self.tgt, self.mode, self.regions, self.ignore_label, self.table, self.smooth,
                                            self.ddp, self.group, counts=self.step_counts, accum=self.counts)
+                if ds_loss is not None:
+                    loss = ds_loss
                 self.loss_sum += loss.double()
         finally:
             self.net.train(was_training)

@@ -33,6 +33,8 @@
  *   du_msda_prep / du_msda_prep_bwd <- ms_deform_attn.py:188-197
  *   du_dice_ce_*                  <- DC_and_CE_loss (training/loss/compound_losses.py:8-56, dice.py:58-119), the loss nnUNetTrainer.train_step
  *          applies to the logits (nnUNetTrainer.py:917); "next" row of the scope table
+ *   du_ds_loss_*, du_downsample_seg <- DeepSupervisionWrapper (training/loss/deep_supervision.py) with the weights of
+ *          nnUNetTrainer._build_loss (nnUNetTrainer.py:373-387) and DownsampleSegForDSTransform2 (deep_supervision_donwsampling.py)
  *   du_dice_ce_masked_*, du_dice_bce_*, du_labels_to_regions
  *       <- the ignore-label and region configurations of nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365):
  *          DC_and_CE_loss(ignore_label) (compound_losses.py:31-56), DC_and_BCE_loss (compound_losses.py:83-99),
@@ -495,6 +497,36 @@ int du_dice_bce_bwd(const float* logits, const uint8_t* target, const float* coe
    region), out (B,R+has_ignore,H*W) uint8: plane r = [seg in region r], plane R = [seg == ignore_label] */
 int du_labels_to_regions(const int64_t* seg, const int64_t* table, uint8_t* out, int B, int R, int64_t HW, int has_ignore,
                          int64_t ignore_label, void* stream);
+
+/* ---- deep supervision: DeepSupervisionWrapper (training/loss/deep_supervision.py) around the three losses above, with the targets of
+        DownsampleSegForDSTransform2 (custom_transforms/deep_supervision_donwsampling.py) gathered in the kernels ----
+   total = sum over the scales with weights[s] != 0, in scale order, of weights[s] * loss_s.  logits / dlogits: HOST arrays of S DEVICE
+   pointers, scale s = (B, C, hs[s], wd[s]) fp32, largest first; hs, wd, weights: HOST arrays of S values, read during the call.  A scale
+   with weight 0 is inactive: its pointer may be NULL, its logits are never read and its gradient is never written.  target (B, H*W)
+   int64: the FULL-resolution label map; the target of scale s at (y, x) is target[src(y, H / hs[s], H), src(x, W / wd[s], W)],
+   src(i, z, n) = floor(clamp((i + 0.5) z - 0.5, 0, n - 1) + 0.5) in fp64, operation by operation what scipy.ndimage.zoom(order=0,
+   mode="nearest", grid_mode=True) computes, i.e. batchgenerators' resize_segmentation(order=0).
+   mode 0: softmax over C = K classes in [2,8], labels in [0,K) or ignore_label (has_ignore), Dice over classes 1..K-1 (CD = K-1);
+   mode 1: sigmoid over C = R regions in [1,8], table (R) int64 DEVICE bit masks as in du_labels_to_regions, Dice over all R (CD = R).
+   sums (S (2 + 3 CD) floats): [(CE or BCE sum, n_valid) per scale | (I_c, P_c, G_c) c < CD per scale]; under data parallelism the caller
+   all-reduces sums[2 S:] (every scale's Dice slice, contiguous) and passes grad_mult = world size.  Zeros for an inactive scale.
+   loss (1 + S floats) = [total, loss_0 .. loss_{S-1}] (0 for an inactive scale); coef (S (2 CD + 1) floats), weights folded in.
+   Launches: du_ds_loss_sums 2 (partial rows of all scales; one block per scale adds its rows in a fixed order: no float atomics),
+   du_ds_loss_finish 1, du_ds_loss_bwd 1 -- four per loss whatever S is.
+   DU_ERR_BAD_ARG: S < 1, a scale larger than the target, a NULL pointer of an active scale, every weight 0, a workspace below
+   du_ds_loss_ws_elems floats; DU_ERR_UNSUPPORTED: S > 4, C outside the ranges above, H or W above 32768. */
+int64_t du_ds_loss_ws_elems(int mode, int B, int C, int H, int W, int S, const int* hs, const int* wd, const float* weights);
+int du_ds_loss_sums(int mode, const float* const* logits, const int64_t* target, const int64_t* table, float* sums, int B, int C, int H,
+                    int W, int S, const int* hs, const int* wd, const float* weights, int has_ignore, int64_t ignore_label, float* ws,
+                    int64_t ws_elems, void* stream);
+int du_ds_loss_finish(int mode, const float* sums, float* loss, float* coef, int C, int S, const float* weights, int has_ignore,
+                      float smooth, float grad_mult, void* stream);
+int du_ds_loss_bwd(int mode, const float* const* logits, const int64_t* target, const int64_t* table, const float* coef,
+                   const float* grad_out, float* const* dlogits, int B, int C, int H, int W, int S, const int* hs, const int* wd,
+                   const float* weights, int has_ignore, int64_t ignore_label, void* stream);
+/* DownsampleSegForDSTransform2 on the device: seg (B, H*W) int64 -> outs[s] (B, hs[s]*wd[s]) int64 for S in [1,4] maps (outs: HOST array
+   of DEVICE pointers), by the index formula above, in one launch */
+int du_downsample_seg(const int64_t* seg, int64_t* const* outs, int B, int H, int W, int S, const int* hs, const int* wd, void* stream);
 
 /* ---- validation step (nnUNetTrainer.validation_step, nnUNetTrainer.py:946-1008 with get_tp_fp_fn_tn, dice.py:122-167): ONE read of the
         logits gives the sums of the matching training loss above (same layout and the same bits: run the matching *_finish on them) and the
