@@ -7,7 +7,10 @@ reference's fp64 fixture 1e-5.
 What each instrument is for.  Random inputs (this file): rounding behaviour and realistic magnitudes -- seeded randn operands at the
 scales the network has, every epilogue, repeat-run screens.  They cannot see a single missing term: at K = 4096 a K loop that stops one
 element short stays below 3e-2.  Exact inputs (tests/test_gpu_exact.py): indexing and completeness of the sum -- integer operands whose
-fp32 sums are exact in any order, compared bit for bit with the fp64 reference, no tolerance."""
+fp32 sums are exact in any order, compared bit for bit with the fp64 reference, no tolerance.  The same two instruments, exact inputs and
+derived per-element bounds, hold the small NHWC kernels (tests/test_gpu_small_ops.py) and the norm kernels (tests/test_gpu_norms.py:
+every sum of csrc/norm.hip to the bit, y / dx / rstd per element, at the edges of every regime switch); the norm tests of this file keep
+the realistic magnitudes."""
 import os
 
 import numpy as np
