@@ -139,23 +139,27 @@ def _export_torch(sums, npred, window, order, out_hw, before, corner, want_probs
     return seg, probs, finite
 
 
-def _export_hip(sums, npred, window, order, out_hw, before, corner, want_probs):
+def _export_hip(sums, npred, window, order, out_hw, before, corner, want_probs, flag=None):
+    """flag: a zeroed int32 element on the device that the caller reads back itself (the cases path reads a group's flags in one copy);
+    None = read here"""
     K, D, Hp, Wp = sums.shape
     y0, x0, Hc, Wc = window
     dev = sums.device
     seg = torch.empty(before, dtype=torch.uint8, device=dev)
     probs = torch.empty((K, *before), dtype=torch.float32, device=dev) if want_probs else None
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    deferred = flag is not None
+    if not deferred:
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
     packed = 0 if order is None else _signed64(sum(c << (8 * i) for i, c in enumerate(order)))
     _lib.check(_lib.lib().du_export_seg(sums.data_ptr(), None if npred is None else npred.data_ptr(), seg.data_ptr(),
                                         None if probs is None else probs.data_ptr(), flag.data_ptr(), K, D, Hp, Wp, y0, x0, Hc, Wc,
                                         out_hw[0], out_hw[1], before[0], before[1], before[2], corner[0], corner[1], corner[2],
                                         EXPORT_SOFTMAX if order is None else EXPORT_REGIONS, packed,
                                         torch.cuda.current_stream().cuda_stream), "du_export_seg")
-    return seg, probs, int(flag.item()) == 0
+    return seg, probs, deferred or int(flag.item()) == 0
 
 
-def _export(sums, npred, window, regions_class_order, properties, transpose_backward, return_probabilities):
+def _export(sums, npred, window, regions_class_order, properties, transpose_backward, return_probabilities, flag=None):
     if sums.ndim != 4:
         raise ValueError("logits must be (K, D, H, W)")
     if sums.dtype != torch.float32:
@@ -167,8 +171,11 @@ def _export(sums, npred, window, regions_class_order, properties, transpose_back
     out_hw, before, corner = _geometry((D, window[2], window[3]), properties)
     sums = sums.contiguous()
     npred = None if npred is None else npred.contiguous()
-    run = _export_hip if sums.is_cuda else _export_torch
-    seg, probs, finite = run(sums, npred, window, order, out_hw, before, corner, return_probabilities)
+    if flag is not None and sums.is_cuda:
+        seg, probs, finite = _export_hip(sums, npred, window, order, out_hw, before, corner, return_probabilities, flag)
+    else:
+        run = _export_hip if sums.is_cuda else _export_torch
+        seg, probs, finite = run(sums, npred, window, order, out_hw, before, corner, return_probabilities)
     if not finite:
         raise RuntimeError("Encountered inf in predicted array")                     # predict_from_raw_data.py:612-615
     seg, probs = _permute(seg, probs, transpose_backward)

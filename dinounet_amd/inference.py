@@ -17,6 +17,15 @@ the checkpoint's inference_allowed_mirroring_axes.  There is no CPU path: the mo
 What follows the logits in the reference (resampling, argmax / region paint, bbox paste, per-case metrics; export_prediction.py:15-68,
 evaluate_predictions.py:152-234) is export.py: predict_segmentation runs the window loop below and goes from the accumulators straight
 to the label map.
+A LIST of cases (predict_from_raw_data.py:330-427, predict_from_list_of_npy_arrays / predict_from_data_iterator, which loop case by case)
+goes through predict_cases_logits / predict_cases_segmentation / predict_from_list_of_npy_arrays and their EnsemblePredictor methods: the
+windows of consecutive cases share window batches (plan_case_batches), so a list of small 2-D cases pays ceil(windows / batch) forwards
+instead of one mostly empty forward per case.  Around the same `forward` two kernels of csrc/window.hip replace the torch glue and the
+atomics: du_window_gather builds a batch straight from several cases, the padding folded in, and du_window_accumulate_cases adds the
+weighted logits with one owner lane per accumulator element in slot order -- the reference's sequential loop in fp32 to the bit,
+reproducible, and independent of which cases share a batch.  The single-case functions are unchanged.
+The importance map is the outer product of the filtered 1-D deltas (equal to filtering the patch, to the bit), memoised per
+(patch, sigma_scale) as the reference memoises it (sliding_window_prediction.py:10).
 `acvl_utils.pad_nd_image` (not vendored in the reference tree) is restated from its published behaviour: centred constant padding
 up to the patch size, extra pixel on the high side."""
 import itertools
@@ -28,14 +37,32 @@ import torch
 from . import _lib
 
 
+_DELTA_CACHE = {}
+
+
+def _filtered_delta(tile_size, sigma_scale):
+    """float64 gaussian_filter(delta at tile // 2, sigma = tile * sigma_scale, mode='constant') without filtering the tile: the filter is
+    separable and every sample but the delta is 0, so each pass multiplies the previous result by the filtered 1-D delta of its axis (all
+    other terms are 0 * w) -- the outer product of the lines, taken in scipy's axis order, is the filtered tile to the bit."""
+    key = (tile_size, sigma_scale)
+    if key not in _DELTA_CACHE:
+        from scipy.ndimage import gaussian_filter
+        g = None
+        for n in tile_size:
+            line = np.zeros(n)
+            line[n // 2] = 1
+            line = gaussian_filter(line, n * sigma_scale, 0, mode="constant", cval=0)
+            g = line if g is None else np.multiply.outer(g, line)
+        _DELTA_CACHE[key] = g
+    return _DELTA_CACHE[key]
+
+
 def compute_gaussian(tile_size, sigma_scale=1.0 / 8, value_scaling_factor=1.0, dtype=torch.float32, device="cpu"):
-    """sliding_window_prediction.py:10-31 (scipy's gaussian_filter of a centred delta, normalised to `value_scaling_factor`)."""
-    from scipy.ndimage import gaussian_filter
-    tmp = np.zeros(tile_size)
-    tmp[tuple(i // 2 for i in tile_size)] = 1
-    g = gaussian_filter(tmp, [i * sigma_scale for i in tile_size], 0, mode="constant", cval=0)
-    g = torch.from_numpy(g)
-    g = g / torch.max(g) * value_scaling_factor
+    """sliding_window_prediction.py:10-31 (scipy's gaussian_filter of a centred delta, normalised to `value_scaling_factor`).
+    The filtered delta comes from _filtered_delta: memoised per (tile_size, sigma_scale), as the reference memoises; everything after it
+    makes new tensors, so the returned map is the caller's own."""
+    g = torch.from_numpy(_filtered_delta(tuple(int(i) for i in tile_size), float(sigma_scale)))
+    g = g / torch.max(g) * value_scaling_factor                # a new tensor: the memoised array is never written
     g = g.type(dtype).to(device)
     g[g == 0] = torch.min(g[g != 0])       # the importance map must not be 0 (division by the accumulated weights)
     return g
@@ -97,9 +124,10 @@ class _WindowForward:
 
     def __call__(self, x):
         n = x.shape[0]
-        self.x[:n].copy_(x)
-        if n < self.x.shape[0]:
-            self.x[n:].zero_()
+        if n != self.x.shape[0] or x.data_ptr() != self.x.data_ptr():       # (the cases path gathers straight into self.x: nothing to copy)
+            self.x[:n].copy_(x)
+            if n < self.x.shape[0]:
+                self.x[n:].zero_()
         self.graph.replay()
         return self.y
 
@@ -141,25 +169,34 @@ def _accumulate_windows(net, data, patch_size, tile_step_size, use_gaussian, bat
     was_training = net.training
     net.eval()
     try:
-        def eager_forward(xb):
-            out = net(xb)
-            if isinstance(out, (list, tuple)):
-                out = out[0]
-            return out.float().contiguous()
-
-        def graph_forward(xb):
-            # cached on the module: replays read the parameters / running statistics in place, so the capture stays valid
-            # while they are updated (not if they are re-allocated: clear_window_cache(net) then)
-            cache = net.__dict__.setdefault("_sw_forward_cache", {})
-            key = (batch_size, xb.shape[1], xb.shape[2], xb.shape[3], str(dev))
-            if key not in cache:
-                cache[key] = _WindowForward(net, (batch_size, *xb.shape[1:]), dev)
-            return cache[key](xb)
-
-        return _window_loop(graph_forward if graph else eager_forward, dev, data, patch_size, tile_step_size, use_gaussian, batch_size,
+        return _window_loop(_net_forward(net, dev, batch_size, graph), dev, data, patch_size, tile_step_size, use_gaussian, batch_size,
                             mirror_axes)
     finally:
         net.train(was_training)
+
+
+def _net_forward(net, dev, batch_size, graph):
+    """the `forward` of the window loops for one network (in eval mode while it is called): eager, or the captured full window batch"""
+    def eager_forward(xb):
+        out = net(xb)
+        if isinstance(out, (list, tuple)):
+            out = out[0]
+        return out.float().contiguous()
+
+    def captured(C, ph, pw):
+        # cached on the module: replays read the parameters / running statistics in place, so the capture stays valid
+        # while they are updated (not if they are re-allocated: clear_window_cache(net) then)
+        cache = net.__dict__.setdefault("_sw_forward_cache", {})
+        key = (batch_size, C, ph, pw, str(dev))
+        if key not in cache:
+            cache[key] = _WindowForward(net, (batch_size, C, ph, pw), dev)
+        return cache[key]
+
+    def graph_forward(xb):
+        return captured(*xb.shape[1:])(xb)
+
+    graph_forward.static_input = lambda C, ph, pw: captured(C, ph, pw).x      # _window_loop_cases gathers into it
+    return graph_forward if graph else eager_forward
 
 
 def _window_loop(forward, dev, data, patch_size, tile_step_size, use_gaussian, batch_size, mirror_axes):
@@ -207,6 +244,255 @@ def predict_sliding_window_logits(net, data, patch_size, tile_step_size=0.5, use
     if not math.isfinite(float(pred.abs().max())):
         raise RuntimeError("Encountered inf in predicted array")                                 # :612-615
     return pred[:, :, ys, xs]
+
+
+# ------------------------------------------------------------------------------------------------ a list of cases: windows batched across cases
+MAX_WINDOW_BATCH = 64               # du_window_accumulate_cases: one ballot bit per slot of a launch
+
+
+def _padded_shape(shape, patch_size):
+    D, H, W = (int(i) for i in shape)
+    return D, max(H, int(patch_size[0])), max(W, int(patch_size[1]))
+
+
+def plan_case_batches(shapes, patch_size, tile_step_size, batch_size, max_voxels_in_flight=2 ** 26):
+    """Which windows share a forward when a list of cases is predicted.  shapes: (D, H, W) of every case.  Consecutive cases are grouped
+    greedily: a case joins the current group unless the group is non-empty and the accumulator voxels D * Hp * Wp of the group (Hp, Wp: the
+    padded frame of pad_to_patch) would exceed max_voxels_in_flight; a case larger than the budget is a group of its own.  The windows of a
+    group form one list -- cases in list order, each case's windows in sliding_window_origins order -- cut into consecutive chunks of
+    batch_size, so only a group's last chunk can be ragged.  Returns [(case indices, [chunk, ...]), ...] with chunk = [(case, d, y0, x0),
+    ...], `case` the index into `shapes`, y0 / x0 in the padded frame.  Forwards: count_case_forwards."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be positive")
+    padded = [_padded_shape(s, patch_size) for s in shapes]
+    groups, current, voxels = [], [], 0
+    for i, (D, Hp, Wp) in enumerate(padded):
+        if current and voxels + D * Hp * Wp > max_voxels_in_flight:
+            groups.append(current)
+            current, voxels = [], 0
+        current.append(i)
+        voxels += D * Hp * Wp
+    if current:
+        groups.append(current)
+    plan = []
+    for members in groups:
+        windows = [(i, d, y0, x0) for i in members for d, y0, x0 in sliding_window_origins(padded[i], patch_size, tile_step_size)]
+        plan.append((members, [windows[j:j + batch_size] for j in range(0, len(windows), batch_size)]))
+    return plan
+
+
+def count_case_forwards(plan, mirror_axes=None):
+    """network forwards of a plan: one per chunk, times 1 + the number of mirror combinations"""
+    return sum(len(chunks) for _, chunks in plan) * (1 + len(mirror_axes_combinations(mirror_axes, 4)))
+
+
+def _gather_cases_numpy(cases, desc, patch_size, slots=None):
+    """du_window_gather on the host: cases = float32 arrays (C, D, H, W), desc = [(case, d, y0, x0), ...] -> x (slots, C, ph, pw) float32.
+    Element (y, x) of a window reads source row y0 + y - lo_y, column x0 + x - lo_x of its case; outside the image it is 0, and so are the
+    slots after the last descriptor."""
+    ph, pw = int(patch_size[0]), int(patch_size[1])
+    C = cases[0].shape[0]
+    x = np.zeros((len(desc) if slots is None else slots, C, ph, pw), dtype=np.float32)
+    for s, (i, d, y0, x0) in enumerate(desc):
+        H, W = cases[i].shape[2:]
+        sy = y0 + np.arange(ph) - (max(H, ph) - H) // 2
+        sx = x0 + np.arange(pw) - (max(W, pw) - W) // 2
+        iy, ix = np.flatnonzero((sy >= 0) & (sy < H)), np.flatnonzero((sx >= 0) & (sx < W))
+        x[s][:, iy[:, None], ix[None, :]] = np.asarray(cases[i], dtype=np.float32)[:, d][:, sy[iy][:, None], sx[ix][None, :]]
+    return x
+
+
+def _accumulate_cases_numpy(logits, gauss, desc, preds, npreds):
+    """du_window_accumulate_cases on the host, float32, in place: logits (nb, K, ph, pw), gauss (ph, pw), desc = [(case, d, y0, x0), ...],
+    preds[case] (K, D, Hp, Wp), npreds[case] (D, Hp, Wp).  As the kernel: slot b owns the elements of its window that no lower slot of the
+    same case and slice covers; an owned element is read once, gets the rounded product logit * g (npred: g) of every covering slot added
+    in slot order, and is written once."""
+    logits, gauss = np.asarray(logits, dtype=np.float32), np.asarray(gauss, dtype=np.float32)
+    nb, K, ph, pw = logits.shape
+    yy, xx = np.mgrid[0:ph, 0:pw]
+
+    def covers(j, Y, X):
+        return (Y >= desc[j][2]) & (Y < desc[j][2] + ph) & (X >= desc[j][3]) & (X < desc[j][3] + pw)
+
+    for b, (i, d, y0, x0) in enumerate(desc):
+        Y, X = yy + y0, xx + x0
+        meets = [j for j in range(nb) if j != b and desc[j][0] == i and desc[j][1] == d]
+        owned = np.ones((ph, pw), dtype=bool)
+        for j in meets:
+            if j < b:
+                owned &= ~covers(j, Y, X)
+        Y, X = Y[owned], X[owned]
+        acc, acc_n = preds[i][:, d, Y, X], npreds[i][d, Y, X]                       # the one read (fancy indexing copies)
+        for j in [b] + [j for j in meets if j > b]:
+            c = covers(j, Y, X)
+            yj, xj = Y[c] - desc[j][2], X[c] - desc[j][3]
+            g = gauss[yj, xj]
+            acc[:, c] = acc[:, c] + logits[j][:, yj, xj] * g                        # float32: the product is rounded, then added
+            acc_n[c] = acc_n[c] + g
+        preds[i][:, d, Y, X], npreds[i][d, Y, X] = acc, acc_n                       # the one write
+
+
+def _check_cases(list_of_data, batch_size, properties=None):
+    """the ValueErrors of the cases path, before any launch; returns the cases as tensors"""
+    if isinstance(list_of_data, (torch.Tensor, np.ndarray)) or len(list_of_data) == 0:
+        raise ValueError("list_of_data must be a non-empty list of (C, D, H, W) arrays")
+    cases = [torch.as_tensor(c) for c in list_of_data]
+    for i, c in enumerate(cases):
+        if c.ndim != 4 or c.numel() == 0:
+            raise ValueError(f"case {i} must be a 4D tensor (c, d, y, x), got shape {tuple(c.shape)}")
+        if c.shape[0] != cases[0].shape[0]:
+            raise ValueError(f"case {i} has {c.shape[0]} channels, case 0 has {cases[0].shape[0]}")
+    if not 1 <= int(batch_size) <= MAX_WINDOW_BATCH:
+        raise ValueError(f"batch_size must be in 1..{MAX_WINDOW_BATCH} on the cases path, got {batch_size}")
+    if properties is not None and (isinstance(properties, dict) or len(properties) != len(cases)):
+        raise ValueError(f"properties must be a list with one entry per case ({len(cases)})")
+    return cases
+
+
+def _window_loop_cases(forward, dev, cases, patch_size, tile_step_size, use_gaussian, batch_size, mirror_axes, sink, full_batch=False,
+                       max_voxels_in_flight=2 ** 26):
+    """The sibling of _window_loop for a list of (C, D, H, W) cases, with the same `forward`: the windows of consecutive cases share window
+    batches (plan_case_batches).  Per group the accumulators are allocated and the tables uploaded once; per chunk du_window_gather builds the
+    batch straight from the cases (no padded copy), _mirror_and_predict runs as in _window_loop, and du_window_accumulate_cases adds the
+    weighted logits without float atomics, in the reference's order.  full_batch: gather all batch_size slots (zeros after the last window)
+    -- the static buffer of a captured forward, which the gather then writes directly (forward.static_input) unless mirroring needs the
+    un-flipped batch kept; otherwise a ragged chunk is a smaller batch.  When a group is done, sink([(case index, pred
+    (K, D, Hp, Wp), npred (D, Hp, Wp), (y slice, x slice)), ...]) gets the un-normalised accumulators, which are dropped after it returns."""
+    ph, pw = int(patch_size[0]), int(patch_size[1])
+    plan = plan_case_batches([c.shape[1:] for c in cases], (ph, pw), tile_step_size, batch_size, max_voxels_in_flight)
+    gauss = (compute_gaussian((ph, pw), sigma_scale=1.0 / 8, value_scaling_factor=10, dtype=torch.float32, device=dev)
+             if use_gaussian else torch.ones((ph, pw), dtype=torch.float32, device=dev)).contiguous()
+    combos = mirror_axes_combinations(mirror_axes, 4)
+    L = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    C = int(cases[0].shape[0])
+    # a captured forward offers its static input: the gather writes the batch there and the replay copies nothing.  Not with mirroring:
+    # the flipped batches go through that buffer while the un-flipped one is still needed.
+    static = getattr(forward, "static_input", None) if full_batch and not combos else None
+    xbuf = static(C, ph, pw) if static is not None else torch.empty((batch_size, C, ph, pw), dtype=torch.float32, device=dev)
+    for members, chunks in plan:
+        local = {i: j for j, i in enumerate(members)}
+        vols = [cases[i].to(dev, torch.float32).contiguous() for i in members]
+        n = len(vols)
+        # the group's tables, one host->device copy each: source pointers, geometries, every window of the group
+        src = torch.tensor([v.data_ptr() for v in vols], dtype=torch.int64).to(dev)
+        geom = torch.tensor([list(v.shape[1:]) for v in vols], dtype=torch.int32).to(dev)
+        desc_all = torch.tensor([[local[i], d, y0, x0] for chunk in chunks for i, d, y0, x0 in chunk], dtype=torch.int32).to(dev)
+        preds = npreds = acc = None
+        w0 = 0
+        for chunk in chunks:
+            nb = len(chunk)
+            slots = batch_size if full_batch else nb
+            x, desc = xbuf[:slots], desc_all[w0:w0 + nb]
+            w0 += nb
+            _lib.check(L.du_window_gather(src.data_ptr(), geom.data_ptr(), desc.data_ptr(), x.data_ptr(), n, nb, slots, C, ph, pw, st),
+                       "du_window_gather")
+            logits = _mirror_and_predict(forward, x, combos)
+            if (logits.ndim != 4 or logits.shape[0] < nb or tuple(logits.shape[2:]) != (ph, pw) or logits.dtype != torch.float32
+                    or not logits.is_contiguous() or logits.device != xbuf.device):
+                raise RuntimeError(f"forward must return contiguous fp32 logits (>= {nb}, K, {ph}, {pw}) on the device, got "
+                                   f"{tuple(logits.shape)} {logits.dtype}")
+            K = int(logits.shape[1])
+            if preds is None:                                              # (the number of heads is known after the first forward)
+                shapes = [_padded_shape(v.shape[1:], (ph, pw)) for v in vols]
+                preds = [torch.zeros((K, *s), dtype=torch.float32, device=dev) for s in shapes]
+                npreds = [torch.zeros(s, dtype=torch.float32, device=dev) for s in shapes]
+                acc = torch.tensor([[p.data_ptr() for p in preds], [p.data_ptr() for p in npreds]], dtype=torch.int64).to(dev)
+            elif K != preds[0].shape[0]:
+                raise RuntimeError(f"forward returned {K} heads after {preds[0].shape[0]}")
+            _lib.check(L.du_window_accumulate_cases(logits.data_ptr(), gauss.data_ptr(), desc.data_ptr(), geom.data_ptr(), acc[0].data_ptr(),
+                                                    acc[1].data_ptr(), n, nb, K, ph, pw, st), "du_window_accumulate_cases")
+        group = []
+        for j, i in enumerate(members):
+            H, W = (int(e) for e in vols[j].shape[2:])
+            lo_y, lo_x = (max(H, ph) - H) // 2, (max(W, pw) - W) // 2
+            group.append((i, preds[j], npreds[j], (slice(lo_y, lo_y + H), slice(lo_x, lo_x + W))))
+        sink(group)
+        del group, preds, npreds, vols
+
+
+def _raise_non_finite(bad_cases):
+    raise RuntimeError(f"Encountered inf in predicted array (cases {bad_cases})")                # :612-615
+
+
+def _logits_sink(out):
+    """sink of _window_loop_cases: normalise, check, un-pad.  One synchronising read-back per group: the cases' maxima together."""
+    def sink(group):
+        L = _lib.lib()
+        st = torch.cuda.current_stream().cuda_stream
+        worst = []
+        for _, pred, npred, _ in group:
+            _lib.check(L.du_window_normalize(pred.data_ptr(), npred.data_ptr(), pred.shape[0], npred.numel(), st), "du_window_normalize")
+            worst.append(torch.stack(torch.aminmax(pred)))                         # (no |pred| temporary; a NaN comes through both)
+        finite = torch.isfinite(torch.stack(worst)).all(1).tolist()
+        if not all(finite):
+            _raise_non_finite([g[0] for g, ok in zip(group, finite) if not ok])
+        for i, pred, _, (ys, xs) in group:
+            out[i] = pred[:, :, ys, xs]
+    return sink
+
+
+def _segmentation_sink(out, dev, regions_class_order, properties, transpose_backward, return_probabilities):
+    """sink of _window_loop_cases: export._export of every case from its un-normalised accumulators; the non-finite flags of a group sit in
+    one tensor and are read back together"""
+    from . import export
+
+    def sink(group):
+        flags = torch.zeros(len(group), dtype=torch.int32, device=dev)
+        for j, (i, pred, npred, (ys, xs)) in enumerate(group):
+            window = (ys.start, xs.start, ys.stop - ys.start, xs.stop - xs.start)
+            out[i] = export._export(pred, npred, window, regions_class_order, None if properties is None else properties[i],
+                                    transpose_backward, return_probabilities, flag=flags[j:j + 1])
+        raised = flags.tolist()
+        if any(raised):
+            _raise_non_finite([g[0] for g, f in zip(group, raised) if f])
+    return sink
+
+
+@torch.no_grad()
+def _accumulate_cases(net, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight):
+    """_accumulate_windows for a list of cases: the network in eval mode around _window_loop_cases"""
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("sliding-window inference runs on the MI355X (no CPU fallback)")
+    was_training = net.training
+    net.eval()
+    try:
+        _window_loop_cases(_net_forward(net, dev, batch_size, graph), dev, cases, patch_size, tile_step_size, use_gaussian, batch_size,
+                           mirror_axes, sink, full_batch=graph, max_voxels_in_flight=max_voxels_in_flight)
+    finally:
+        net.train(was_training)
+
+
+@torch.no_grad()
+def predict_cases_logits(net, list_of_data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False, mirror_axes=None,
+                         *, max_voxels_in_flight=2 ** 26):
+    """predict_sliding_window_logits for a list of (C, D, H, W) cases of any sizes (one channel count) -> list of fp32 logits (K, D, H, W) on
+    the GPU.  Windows of consecutive cases share window batches (plan_case_batches: sum over groups of ceil(windows / batch_size) forwards
+    instead of one or more per case), which is what small 2-D cases need; the accumulation has no float atomics, so a case's logits are
+    reproducible and do not depend on the cases it shares batches with.  batch_size <= 64.  max_voxels_in_flight bounds the accumulator
+    voxels of the cases that are open at a time."""
+    cases = _check_cases(list_of_data, batch_size)
+    out = [None] * len(cases)
+    _accumulate_cases(net, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, _logits_sink(out),
+                      max_voxels_in_flight)
+    return out
+
+
+@torch.no_grad()
+def predict_cases_segmentation(net, list_of_data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
+                               mirror_axes=None, *, regions_class_order=None, properties=None, transpose_backward=None,
+                               return_probabilities=False, max_voxels_in_flight=2 ** 26):
+    """export.predict_segmentation for a list of cases: the window loop over the list (predict_cases_logits), then every case goes from its
+    un-normalised accumulators to its label map in one pass.  properties: None or one dict per case.  Returns a list of uint8 label maps,
+    with return_probabilities a list of (seg, probs)."""
+    cases = _check_cases(list_of_data, batch_size, properties)
+    dev = next(net.parameters()).device
+    out = [None] * len(cases)
+    sink = _segmentation_sink(out, dev, regions_class_order, properties, transpose_backward, return_probabilities)
+    _accumulate_cases(net, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight)
+    return out
 
 
 def _training_flags(module):
@@ -303,11 +589,16 @@ class EnsemblePredictor:
         if not graph:
             return self._eager_forward
 
-        def graph_forward(xb):
-            key = (batch_size, xb.shape[1], xb.shape[2], xb.shape[3])
+        def captured(C, ph, pw):
+            key = (batch_size, C, ph, pw)
             if key not in self._forward_cache:                             # backbone + F heads: one graph per (batch, C, patch)
-                self._forward_cache[key] = _WindowForward(self._eager_forward, (batch_size, *xb.shape[1:]), self.device)
-            return self._forward_cache[key](xb)
+                self._forward_cache[key] = _WindowForward(self._eager_forward, (batch_size, C, ph, pw), self.device)
+            return self._forward_cache[key]
+
+        def graph_forward(xb):
+            return captured(*xb.shape[1:])(xb)
+
+        graph_forward.static_input = lambda C, ph, pw: captured(C, ph, pw).x
         return graph_forward
 
     @torch.no_grad()
@@ -346,6 +637,46 @@ class EnsemblePredictor:
         window = (ys.start, xs.start, ys.stop - ys.start, xs.stop - xs.start)
         return export._export(pred, npred, window, regions_class_order, properties, transpose_backward, return_probabilities)
 
+    @torch.no_grad()
+    def _accumulate_cases(self, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight):
+        """_accumulate for a list of cases (_window_loop_cases): every case's n_predictions is scaled by F before `sink` sees it"""
+        folds = float(len(self.nets))
+
+        def scaled(group):
+            if folds > 1:
+                for _, _, npred, _ in group:
+                    npred.mul_(folds)
+            sink(group)
+
+        modes = _training_flags(self.backbone)
+        self.backbone.eval()
+        try:
+            _window_loop_cases(self._forward(batch_size, graph), self.device, cases, patch_size, tile_step_size, use_gaussian, batch_size,
+                               mirror_axes, scaled, full_batch=graph, max_voxels_in_flight=max_voxels_in_flight)
+        finally:
+            _set_training_flags(modes)
+
+    @torch.no_grad()
+    def predict_cases_logits(self, list_of_data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
+                             mirror_axes=None, *, max_voxels_in_flight=2 ** 26):
+        """predict_cases_logits of the ensemble: per case the mean over the folds of the logits (K, D, H, W), fp32 on the GPU"""
+        cases = _check_cases(list_of_data, batch_size)
+        out = [None] * len(cases)
+        self._accumulate_cases(cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, _logits_sink(out),
+                               max_voxels_in_flight)
+        return out
+
+    @torch.no_grad()
+    def predict_cases_segmentation(self, list_of_data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
+                                   mirror_axes=None, *, regions_class_order=None, properties=None, transpose_backward=None,
+                                   return_probabilities=False, max_voxels_in_flight=2 ** 26):
+        """predict_cases_segmentation of the ensemble: a list of label maps (or of (seg, probs))"""
+        cases = _check_cases(list_of_data, batch_size, properties)
+        out = [None] * len(cases)
+        sink = _segmentation_sink(out, self.device, regions_class_order, properties, transpose_backward, return_probabilities)
+        self._accumulate_cases(cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight)
+        return out
+
     def predict_from_raw(self, data, properties, patch_size, **kwargs):
         """preprocessing.predict_from_raw with this ensemble in place of one network: raw array in, ensemble label map out"""
         from .preprocessing import predict_from_raw
@@ -356,3 +687,64 @@ class EnsemblePredictor:
 from .export import case_metrics, logits_to_segmentation, predict_segmentation  # noqa: E402,F401
 # ... and what precedes the window loop (crop, normalise, resample a raw case) in preprocessing.py: raw array in, label map out
 from .preprocessing import predict_from_raw  # noqa: E402,F401
+
+
+@torch.no_grad()
+def predict_from_list_of_npy_arrays(net_or_predictor, image_or_list_of_images, properties_or_list_of_properties, patch_size, *,
+                                    transpose_forward, spacing, normalization_schemes, use_mask_for_norm,
+                                    foreground_intensity_properties_per_channel, list_of_parameters=None, **predict_kwargs):
+    """nnUNetPredictor.predict_from_list_of_npy_arrays (predict_from_raw_data.py:330-427) without files: raw (C, X, Y, Z) arrays (numpy or
+    torch) and their properties dicts in, the list of uint8 label maps in the raw geometries out.  preprocessing.run_case per case (it fills
+    each properties dict, as for predict_from_raw), then the cases path -- predict_cases_segmentation with every case's properties and
+    transpose_backward = the inverse of transpose_forward -- so the windows of small cases share forwards.  A single array with a single
+    dict is accepted (the result is still a list).  net_or_predictor: a network (optionally with list_of_parameters = the folds' parameter
+    sets) or an EnsemblePredictor.  predict_kwargs: those of predict_cases_segmentation.  The list is checked as a whole before anything is
+    launched; then it is preprocessed and predicted group by group (the groups of plan_case_batches under max_voxels_in_flight), so only one
+    group's preprocessed cases and accumulators are on the device at a time."""
+    from .preprocessing import _check_transpose, run_case
+    if isinstance(image_or_list_of_images, (np.ndarray, torch.Tensor)):
+        if not isinstance(properties_or_list_of_properties, dict):
+            raise ValueError("a single image goes with a single properties dict")
+        images, props = [image_or_list_of_images], [properties_or_list_of_properties]
+    else:
+        images, props = list(image_or_list_of_images), properties_or_list_of_properties
+        if isinstance(props, dict) or props is None or len(props) != len(images):
+            raise ValueError(f"properties must be a list with one dict per image ({len(images)})")
+        props = list(props)
+    for k in ("properties", "transpose_backward"):
+        if k in predict_kwargs:
+            raise ValueError(f"predict_from_list_of_npy_arrays derives {k} itself")
+    # every ValueError of the list before anything is launched (run_case would meet a bad case only after its predecessors ran)
+    images = _check_cases(images, predict_kwargs.get("batch_size", 8))
+    for j, q in enumerate(props):
+        if not isinstance(q, dict) or "spacing" not in q or len(q["spacing"]) != 3:
+            raise ValueError(f"properties of case {j} must be a dict whose 'spacing' holds the three raw spacings")
+    tf = _check_transpose(transpose_forward)
+    if list_of_parameters is not None:
+        if isinstance(net_or_predictor, EnsemblePredictor):
+            raise ValueError("list_of_parameters goes with a network, not with an EnsemblePredictor")
+        net_or_predictor = EnsemblePredictor(net_or_predictor, list_of_parameters)
+    transpose_backward = [tf.index(i) for i in range(3)]
+    budget = predict_kwargs.get("max_voxels_in_flight", 2 ** 26)
+    out, pre, first, voxels = [], [], 0, 0
+
+    def flush():
+        if isinstance(net_or_predictor, EnsemblePredictor):
+            return net_or_predictor.predict_cases_segmentation(pre, patch_size, properties=props[first:first + len(pre)],
+                                                               transpose_backward=transpose_backward, **predict_kwargs)
+        return predict_cases_segmentation(net_or_predictor, pre, patch_size, properties=props[first:first + len(pre)],
+                                          transpose_backward=transpose_backward, **predict_kwargs)
+
+    # group by group, by the rule of plan_case_batches: the preprocessed cases of one group are all that is held at a time, and as window
+    # batches never span groups the label maps are those of one call on the whole list
+    for j, (img, q) in enumerate(zip(images, props)):
+        case = run_case(img, None, q, transpose_forward=tf, spacing=spacing, normalization_schemes=normalization_schemes,
+                        use_mask_for_norm=use_mask_for_norm,
+                        foreground_intensity_properties_per_channel=foreground_intensity_properties_per_channel)[0]
+        D, Hp, Wp = _padded_shape(case.shape[1:], patch_size)
+        if pre and voxels + D * Hp * Wp > budget:
+            out += flush()
+            pre, first, voxels = [], j, 0
+        pre.append(case)
+        voxels += D * Hp * Wp
+    return out + flush()

@@ -675,6 +675,21 @@ int du_debug_attn_census(uint64_t* host, int n);
 int du_window_accumulate(const float* logits, const float* gauss, const int32_t* coords, float* pred, float* npred, int nb, int K,
                          int ph, int pw, int D, int H, int W, void* stream);
 int du_window_normalize(float* pred, const float* npred, int K, int64_t n, void* stream);
+/* ... over a LIST of cases, one window batch holding windows of several of them (csrc/window.hip).  All tables are DEVICE arrays:
+   geom (ncases, 3) int32 = (D, H, W) of each case; desc (nb, 4) int32 on 16 bytes = (case, d, y0, x0) of each window, y0 / x0 in the case's
+   padded frame Hp = max(H, ph), lo_y = (Hp - H) / 2, likewise x (pad_nd_image: centred, the odd pixel on the high side).
+   du_window_gather: cases = table of ncases pointers to contiguous fp32 (C, D, H, W) volumes; x (slots, C, ph, pw) fp32 = the windows, a source
+   position outside the image reads as 0, slots nb .. slots-1 are written as zeros.  A pure copy.
+   du_window_accumulate_cases: logits (nb, K, ph, pw), gauss (ph, pw); preds / npreds = tables of the cases' accumulators (K, D, Hp, Wp) and
+   (D, Hp, Wp).  No float atomics: every accumulator element is read once, gets acc = fadd(acc, fmul(logit, g)) (npred: acc + g) of every
+   covering slot of the launch in slot order, and is written once -- equal to the reference's sequential loop in fp32 to the bit when a case's
+   windows arrive in its order (launches of one stream are ordered).  A descriptor that does not fit its case is skipped (gather: zeros).
+   DU_ERR_BAD_ARG: a NULL pointer, a non-positive size, slots < nb, desc not on 16 bytes; DU_ERR_UNSUPPORTED: nb > 64 (accumulate), ph pw >=
+   2^29; both before any launch. */
+int du_window_gather(const void* const* cases, const int32_t* geom, const int32_t* desc, float* x, int ncases, int nb, int slots, int C,
+                     int ph, int pw, void* stream);
+int du_window_accumulate_cases(const float* logits, const float* gauss, const int32_t* desc, const int32_t* geom, float* const* preds,
+                               float* const* npreds, int ncases, int nb, int K, int ph, int pw, void* stream);
 
 /* ---- export tail: accumulators -> label map in the case's original geometry, in ONE pass
    (convert_predicted_logits_to_segmentation_with_correct_shape, dinounet/inference/export_prediction.py:15-68, with
