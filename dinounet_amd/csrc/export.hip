@@ -1,4 +1,4 @@
-// Export tail of the sliding-window predictor: the accumulators of du_window_accumulate go straight to the label map of the
+// Export tail of the sliding-window predictor: the accumulators of du_window_accumulate_cases go straight to the label map of the
 // case's original geometry, and two label maps go to the per-case counts.
 //   convert_predicted_logits_to_segmentation_with_correct_shape (dinounet/inference/export_prediction.py:15-68):
 //     resample the logits in-plane to shape_after_cropping_and_before_resampling (order 1, edge clamp, half-pixel centres),

@@ -204,10 +204,12 @@ def predict_segmentation(net, data, patch_size, tile_step_size=0.5, use_gaussian
     inference.predict_sliding_window_logits, then ONE pass from the accumulators (still padded, not divided) to the label map -- no
     normalise, isfinite or slice pass over the K planes."""
     from . import inference
-    pred, npred, (ys, xs) = inference._accumulate_windows(net, data, patch_size, tile_step_size, use_gaussian, batch_size, graph,
-                                                          mirror_axes)
-    window = (ys.start, xs.start, ys.stop - ys.start, xs.stop - xs.start)
-    return _export(pred, npred, window, regions_class_order, properties, transpose_backward, return_probabilities)
+    assert data.ndim == 4, "input_image must be a 4D tensor (c, d, y, x)"
+    out = [None]
+    sink = inference._segmentation_sink(out, regions_class_order, None if properties is None else [properties], transpose_backward,
+                                        return_probabilities, named=False)
+    inference._accumulate_cases(net, [data], patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink)
+    return out[0]
 
 
 def _region_mask_bits(region_or_label):

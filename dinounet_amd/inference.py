@@ -9,8 +9,8 @@ dinounet/inference/sliding_window_prediction.py:10-60 Gaussian map and step posi
 
 Differences from the reference, all on purpose: windows are run through the network in batches (the reference predicts one window
 per forward); the accumulators are fp32 (the reference keeps fp16 buffers and aborts on overflow, :612-615); the weighted
-accumulate and the final division are two HIP kernels (csrc/elementwise.hip: du_window_accumulate, du_window_normalize) instead of
-two indexed read-modify-write torch ops per window.  Test-time mirroring (predict_from_raw_data.py:537-552: the prediction is
+accumulate and the final division are two HIP kernels (csrc/window.hip: du_window_accumulate_cases, csrc/elementwise.hip:
+du_window_normalize) instead of two indexed read-modify-write torch ops per window.  Test-time mirroring (predict_from_raw_data.py:537-552: the prediction is
 averaged with the un-flipped predictions of every non-empty combination of the allowed mirror axes) is available through
 mirror_axes=...; the in-trainer validation passes use_mirroring=False (nnUNetTrainer.py:1160), the stand-alone predictor defaults to
 the checkpoint's inference_allowed_mirroring_axes.  There is no CPU path: the module needs the GPU.
@@ -20,16 +20,17 @@ to the label map.
 A LIST of cases (predict_from_raw_data.py:330-427, predict_from_list_of_npy_arrays / predict_from_data_iterator, which loop case by case)
 goes through predict_cases_logits / predict_cases_segmentation / predict_from_list_of_npy_arrays and their EnsemblePredictor methods: the
 windows of consecutive cases share window batches (plan_case_batches), so a list of small 2-D cases pays ceil(windows / batch) forwards
-instead of one mostly empty forward per case.  Around the same `forward` two kernels of csrc/window.hip replace the torch glue and the
-atomics: du_window_gather builds a batch straight from several cases, the padding folded in, and du_window_accumulate_cases adds the
-weighted logits with one owner lane per accumulator element in slot order -- the reference's sequential loop in fp32 to the bit,
-reproducible, and independent of which cases share a batch.  The single-case functions are unchanged.
+instead of one mostly empty forward per case.  Around the `forward` two kernels of csrc/window.hip stand where torch glue and float
+atomics would: du_window_gather builds a batch straight from several cases, the padding folded in, and du_window_accumulate_cases adds
+the weighted logits with one owner lane per accumulator element in slot order -- the reference's sequential loop in fp32 to the bit,
+reproducible, and independent of which cases share a batch.  There is ONE window loop (_window_loop_cases): the single-case functions run
+it on the list of one, and a network and an EnsemblePredictor go through the same _accumulate_cases.
 The importance map is the outer product of the filtered 1-D deltas (equal to filtering the patch, to the bit), memoised per
 (patch, sigma_scale) as the reference memoises it (sliding_window_prediction.py:10).
 `acvl_utils.pad_nd_image` (not vendored in the reference tree) is restated from its published behaviour: centred constant padding
 up to the patch size, extra pixel on the high side."""
+import contextlib
 import itertools
-import math
 
 import numpy as np
 import torch
@@ -157,96 +158,58 @@ def _mirror_and_predict(forward, x, combos):
     return pred
 
 
-@torch.no_grad()
-def _accumulate_windows(net, data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes):
-    """The window loop shared by predict_sliding_window_logits and export.predict_segmentation: data (C, D, H, W) -> the accumulators
-    predicted_logits (K, D, Hp, Wp) and n_predictions (D, Hp, Wp) of the padded volume (predict_from_raw_data.py:607-608, not yet
-    divided) and the (y, x) slices that undo the padding."""
-    assert data.ndim == 4, "input_image must be a 4D tensor (c, d, y, x)"
-    dev = next(net.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError("sliding-window inference runs on the MI355X (no CPU fallback)")
-    was_training = net.training
-    net.eval()
-    try:
-        return _window_loop(_net_forward(net, dev, batch_size, graph), dev, data, patch_size, tile_step_size, use_gaussian, batch_size,
-                            mirror_axes)
-    finally:
-        net.train(was_training)
+class _NetPredictor:
+    """A plain network in the three things in which it differs from an EnsemblePredictor for the window loop: the forward of a window batch
+    (with the cache its captures live in), what is put into eval mode and restored, and the fold count."""
+    folds = 1
 
+    def __init__(self, net):
+        self.net = net
+        self.device = next(net.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("sliding-window inference runs on the MI355X (no CPU fallback)")
 
-def _net_forward(net, dev, batch_size, graph):
-    """the `forward` of the window loops for one network (in eval mode while it is called): eager, or the captured full window batch"""
-    def eager_forward(xb):
-        out = net(xb)
+    def _eager_forward(self, xb):
+        out = self.net(xb)
         if isinstance(out, (list, tuple)):
             out = out[0]
         return out.float().contiguous()
 
-    def captured(C, ph, pw):
+    def _captures(self):
         # cached on the module: replays read the parameters / running statistics in place, so the capture stays valid
         # while they are updated (not if they are re-allocated: clear_window_cache(net) then)
-        cache = net.__dict__.setdefault("_sw_forward_cache", {})
-        key = (batch_size, C, ph, pw, str(dev))
+        return self.net.__dict__.setdefault("_sw_forward_cache", {}), (str(self.device),)
+
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            yield
+        finally:
+            self.net.train(was_training)
+
+
+def _window_forward(predictor, batch_size, graph):
+    """the `forward` of _window_loop_cases for a predictor (in eval mode while it is called): eager, or the captured full window batch"""
+    if not graph:
+        return predictor._eager_forward
+
+    def captured(C, ph, pw):
+        cache, key_tail = predictor._captures()
+        key = (batch_size, C, ph, pw, *key_tail)
         if key not in cache:
-            cache[key] = _WindowForward(net, (batch_size, C, ph, pw), dev)
+            cache[key] = _WindowForward(predictor._eager_forward, (batch_size, C, ph, pw), predictor.device)
         return cache[key]
 
     def graph_forward(xb):
         return captured(*xb.shape[1:])(xb)
 
     graph_forward.static_input = lambda C, ph, pw: captured(C, ph, pw).x      # _window_loop_cases gathers into it
-    return graph_forward if graph else eager_forward
+    return graph_forward
 
 
-def _window_loop(forward, dev, data, patch_size, tile_step_size, use_gaussian, batch_size, mirror_axes):
-    """The loop itself.  forward(x (b, C, ph, pw)) -> contiguous fp32 logits of at least b windows (a captured forward hands back its whole
-    batch, in a buffer it reuses).  One du_window_accumulate per window batch."""
-    data = data.to(dev, torch.float32)
-    data, (ys, xs) = pad_to_patch(data, patch_size)
-    Cc, D, H, W = data.shape
-    ph, pw = int(patch_size[0]), int(patch_size[1])
-    origins = sliding_window_origins((D, H, W), (ph, pw), tile_step_size)
-    gauss = (compute_gaussian((ph, pw), sigma_scale=1.0 / 8, value_scaling_factor=10, dtype=torch.float32, device=dev)
-             if use_gaussian else torch.ones((ph, pw), dtype=torch.float32, device=dev)).contiguous()
-    pred = npred = None
-    coords_all = torch.tensor(origins, dtype=torch.int32).to(dev)        # one host->device copy for the whole volume
-    L = _lib.lib()
-    st = torch.cuda.current_stream().cuda_stream
-    combos = mirror_axes_combinations(mirror_axes, 4)
-    for i0 in range(0, len(origins), batch_size):
-        chunk = origins[i0:i0 + batch_size]
-        x = torch.stack([data[:, d, y0:y0 + ph, x0:x0 + pw] for d, y0, x0 in chunk])           # (b, C, ph, pw)
-        logits = _mirror_and_predict(forward, x, combos)
-        if combos and logits.shape[0] > len(chunk):
-            logits = logits[:len(chunk)].contiguous()
-        K = logits.shape[1]
-        if pred is None:
-            pred = torch.zeros((K, D, H, W), dtype=torch.float32, device=dev)
-            npred = torch.zeros((D, H, W), dtype=torch.float32, device=dev)
-        coords = coords_all[i0:i0 + len(chunk)]
-        _lib.check(L.du_window_accumulate(logits.data_ptr(), gauss.data_ptr(), coords.data_ptr(), pred.data_ptr(), npred.data_ptr(),
-                                          len(chunk), K, ph, pw, D, H, W, st), "du_window_accumulate")
-    return pred, npred, (ys, xs)
-
-
-@torch.no_grad()
-def predict_sliding_window_logits(net, data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
-                                  mirror_axes=None):
-    """data (C, D, H, W) on the GPU (or host: moved once) -> fp32 logits (K, D, H, W) on the GPU.
-    predict_from_raw_data.py:680-727 with _internal_predict_sliding_window_return_logits :571-621.  graph=True replays a captured
-    forward of a full window batch (worth it from a few batches per volume on).  mirror_axes: allowed_mirroring_axes of the
-    predictor (for this 2D path a subset of (0, 1) = the window's rows / columns), None = no test-time mirroring."""
-    pred, npred, (ys, xs) = _accumulate_windows(net, data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes)
-    K = pred.shape[0]
-    _lib.check(_lib.lib().du_window_normalize(pred.data_ptr(), npred.data_ptr(), K, npred.numel(), torch.cuda.current_stream().cuda_stream),
-               "du_window_normalize")
-    if not math.isfinite(float(pred.abs().max())):
-        raise RuntimeError("Encountered inf in predicted array")                                 # :612-615
-    return pred[:, :, ys, xs]
-
-
-# ------------------------------------------------------------------------------------------------ a list of cases: windows batched across cases
+# ------------------------------------------------------------------------------------------------ the window loop: a list of cases, windows batched across them
 MAX_WINDOW_BATCH = 64               # du_window_accumulate_cases: one ballot bit per slot of a launch
 
 
@@ -352,13 +315,18 @@ def _check_cases(list_of_data, batch_size, properties=None):
 
 def _window_loop_cases(forward, dev, cases, patch_size, tile_step_size, use_gaussian, batch_size, mirror_axes, sink, full_batch=False,
                        max_voxels_in_flight=2 ** 26):
-    """The sibling of _window_loop for a list of (C, D, H, W) cases, with the same `forward`: the windows of consecutive cases share window
-    batches (plan_case_batches).  Per group the accumulators are allocated and the tables uploaded once; per chunk du_window_gather builds the
-    batch straight from the cases (no padded copy), _mirror_and_predict runs as in _window_loop, and du_window_accumulate_cases adds the
-    weighted logits without float atomics, in the reference's order.  full_batch: gather all batch_size slots (zeros after the last window)
+    """The window loop, for a list of (C, D, H, W) cases (a single case is the list of one): the windows of consecutive cases share window
+    batches (plan_case_batches).  forward(x (b, C, ph, pw)) -> contiguous fp32 logits of at least b windows (a captured forward hands back
+    its whole batch, in a buffer it reuses).  Per group the accumulators are allocated and the tables uploaded once; per chunk
+    du_window_gather builds the batch straight from the cases (no padded copy), _mirror_and_predict runs the forward, and
+    du_window_accumulate_cases adds the weighted logits without float atomics, in the reference's order -- a chunk above MAX_WINDOW_BATCH in
+    consecutive launches of at most that many slots.  full_batch: gather all batch_size slots (zeros after the last window)
     -- the static buffer of a captured forward, which the gather then writes directly (forward.static_input) unless mirroring needs the
     un-flipped batch kept; otherwise a ragged chunk is a smaller batch.  When a group is done, sink([(case index, pred
-    (K, D, Hp, Wp), npred (D, Hp, Wp), (y slice, x slice)), ...]) gets the un-normalised accumulators, which are dropped after it returns."""
+    (K, D, Hp, Wp), npred (D, Hp, Wp), (y slice, x slice)), ...]) gets the un-normalised accumulators, which are dropped after it returns.
+    A sink launches its device work and may return a callable that reads the result's non-finite flags back and raises; the loop calls it
+    at once, except the last group's, which it returns: the caller restores the training flags first (host work under the device's last
+    chunks) and synchronises after."""
     ph, pw = int(patch_size[0]), int(patch_size[1])
     plan = plan_case_batches([c.shape[1:] for c in cases], (ph, pw), tile_step_size, batch_size, max_voxels_in_flight)
     gauss = (compute_gaussian((ph, pw), sigma_scale=1.0 / 8, value_scaling_factor=10, dtype=torch.float32, device=dev)
@@ -398,71 +366,101 @@ def _window_loop_cases(forward, dev, cases, patch_size, tile_step_size, use_gaus
                 shapes = [_padded_shape(v.shape[1:], (ph, pw)) for v in vols]
                 preds = [torch.zeros((K, *s), dtype=torch.float32, device=dev) for s in shapes]
                 npreds = [torch.zeros(s, dtype=torch.float32, device=dev) for s in shapes]
-                acc = torch.tensor([[p.data_ptr() for p in preds], [p.data_ptr() for p in npreds]], dtype=torch.int64).to(dev)
+                # the accumulators' pointer table, written by fill launches: an upload at this point would hold the host until the first
+                # forward is through, and with it what the caller does under the device's work (restoring the training flags)
+                acc = torch.empty((2, n), dtype=torch.int64, device=dev)
+                for j in range(n):
+                    acc[0, j], acc[1, j] = preds[j].data_ptr(), npreds[j].data_ptr()
             elif K != preds[0].shape[0]:
                 raise RuntimeError(f"forward returned {K} heads after {preds[0].shape[0]}")
-            _lib.check(L.du_window_accumulate_cases(logits.data_ptr(), gauss.data_ptr(), desc.data_ptr(), geom.data_ptr(), acc[0].data_ptr(),
-                                                    acc[1].data_ptr(), n, nb, K, ph, pw, st), "du_window_accumulate_cases")
+            for s0 in range(0, nb, MAX_WINDOW_BATCH):                      # (launches of one stream are ordered, slots keep window order)
+                _lib.check(L.du_window_accumulate_cases(logits[s0:].data_ptr(), gauss.data_ptr(), desc[s0:].data_ptr(), geom.data_ptr(),
+                                                        acc[0].data_ptr(), acc[1].data_ptr(), n, min(nb - s0, MAX_WINDOW_BATCH), K, ph, pw, st),
+                           "du_window_accumulate_cases")
         group = []
         for j, i in enumerate(members):
             H, W = (int(e) for e in vols[j].shape[2:])
             lo_y, lo_x = (max(H, ph) - H) // 2, (max(W, pw) - W) // 2
             group.append((i, preds[j], npreds[j], (slice(lo_y, lo_y + H), slice(lo_x, lo_x + W))))
-        sink(group)
+        check = sink(group)
         del group, preds, npreds, vols
+        if check is not None and members is not plan[-1][0]:
+            check()
+    return check
 
 
-def _raise_non_finite(bad_cases):
-    raise RuntimeError(f"Encountered inf in predicted array (cases {bad_cases})")                # :612-615
+def _non_finite_check(group, bad, named):
+    """what a sink returns: one synchronising read-back of a group's non-finite flags `bad` (device, one per case), and the reference's
+    error (:612-615).  named: the message lists the cases (not for the single-case functions, which have no list)."""
+    indices = [g[0] for g in group]                                                # (not the group: its accumulators are dropped)
+
+    def check():
+        raised = [i for i, f in zip(indices, bad.tolist()) if f]
+        if raised:
+            raise RuntimeError("Encountered inf in predicted array" + (f" (cases {raised})" if named else ""))
+    return check
 
 
-def _logits_sink(out):
-    """sink of _window_loop_cases: normalise, check, un-pad.  One synchronising read-back per group: the cases' maxima together."""
+def _logits_sink(out, named=True):
+    """sink of _window_loop_cases: normalise, un-pad, and the check of the cases' maxima together"""
     def sink(group):
         L = _lib.lib()
         st = torch.cuda.current_stream().cuda_stream
         worst = []
-        for _, pred, npred, _ in group:
+        for i, pred, npred, (ys, xs) in group:
             _lib.check(L.du_window_normalize(pred.data_ptr(), npred.data_ptr(), pred.shape[0], npred.numel(), st), "du_window_normalize")
             worst.append(torch.stack(torch.aminmax(pred)))                         # (no |pred| temporary; a NaN comes through both)
-        finite = torch.isfinite(torch.stack(worst)).all(1).tolist()
-        if not all(finite):
-            _raise_non_finite([g[0] for g, ok in zip(group, finite) if not ok])
-        for i, pred, _, (ys, xs) in group:
             out[i] = pred[:, :, ys, xs]
+        return _non_finite_check(group, ~torch.isfinite(torch.stack(worst)).all(1), named)
     return sink
 
 
-def _segmentation_sink(out, dev, regions_class_order, properties, transpose_backward, return_probabilities):
+def _segmentation_sink(out, regions_class_order, properties, transpose_backward, return_probabilities, named=True):
     """sink of _window_loop_cases: export._export of every case from its un-normalised accumulators; the non-finite flags of a group sit in
-    one tensor and are read back together"""
+    one tensor and are read back together.  properties: None or one dict per case."""
     from . import export
 
     def sink(group):
-        flags = torch.zeros(len(group), dtype=torch.int32, device=dev)
+        flags = torch.zeros(len(group), dtype=torch.int32, device=group[0][1].device)
         for j, (i, pred, npred, (ys, xs)) in enumerate(group):
             window = (ys.start, xs.start, ys.stop - ys.start, xs.stop - xs.start)
             out[i] = export._export(pred, npred, window, regions_class_order, None if properties is None else properties[i],
                                     transpose_backward, return_probabilities, flag=flags[j:j + 1])
-        raised = flags.tolist()
-        if any(raised):
-            _raise_non_finite([g[0] for g, f in zip(group, raised) if f])
+        return _non_finite_check(group, flags, named)
     return sink
 
 
 @torch.no_grad()
-def _accumulate_cases(net, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight):
-    """_accumulate_windows for a list of cases: the network in eval mode around _window_loop_cases"""
-    dev = next(net.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError("sliding-window inference runs on the MI355X (no CPU fallback)")
-    was_training = net.training
-    net.eval()
-    try:
-        _window_loop_cases(_net_forward(net, dev, batch_size, graph), dev, cases, patch_size, tile_step_size, use_gaussian, batch_size,
-                           mirror_axes, sink, full_batch=graph, max_voxels_in_flight=max_voxels_in_flight)
-    finally:
-        net.train(was_training)
+def _accumulate_cases(net, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight=2 ** 26):
+    """The predictor (a network, or an EnsemblePredictor) in eval mode around _window_loop_cases.  The accumulators hold the SUM over the
+    folds; every case's n_predictions is scaled by the fold count before `sink` sees it, so that sums / n_predictions is the mean logit
+    (one (D, H, W) plane, instead of a pass over the K planes)."""
+    predictor = net if isinstance(net, EnsemblePredictor) else _NetPredictor(net)
+
+    def scaled(group):
+        for _, _, npred, _ in group:
+            npred.mul_(float(predictor.folds))
+        return sink(group)
+
+    with predictor._eval_mode():
+        check = _window_loop_cases(_window_forward(predictor, batch_size, graph), predictor.device, cases, patch_size, tile_step_size,
+                                   use_gaussian, batch_size, mirror_axes, sink if predictor.folds == 1 else scaled, full_batch=graph,
+                                   max_voxels_in_flight=max_voxels_in_flight)
+    check()                            # the last group's read-back, after the flags: restoring them overlaps the device's last chunks
+
+
+@torch.no_grad()
+def predict_sliding_window_logits(net, data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
+                                  mirror_axes=None):
+    """data (C, D, H, W) on the GPU (or host: moved once) -> fp32 logits (K, D, H, W) on the GPU.
+    predict_from_raw_data.py:680-727 with _internal_predict_sliding_window_return_logits :571-621.  graph=True replays a captured
+    forward of a full window batch (worth it from a few batches per volume on).  mirror_axes: allowed_mirroring_axes of the
+    predictor (for this 2D path a subset of (0, 1) = the window's rows / columns), None = no test-time mirroring.  The case runs as the
+    list of one (predict_cases_logits; any positive batch_size), so the logits are reproducible and in the reference's summation order."""
+    assert data.ndim == 4, "input_image must be a 4D tensor (c, d, y, x)"
+    out = [None]
+    _accumulate_cases(net, [data], patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, _logits_sink(out, named=False))
+    return out[0]
 
 
 @torch.no_grad()
@@ -472,7 +470,7 @@ def predict_cases_logits(net, list_of_data, patch_size, tile_step_size=0.5, use_
     the GPU.  Windows of consecutive cases share window batches (plan_case_batches: sum over groups of ceil(windows / batch_size) forwards
     instead of one or more per case), which is what small 2-D cases need; the accumulation has no float atomics, so a case's logits are
     reproducible and do not depend on the cases it shares batches with.  batch_size <= 64.  max_voxels_in_flight bounds the accumulator
-    voxels of the cases that are open at a time."""
+    voxels of the cases that are open at a time.  `net`: a network, or an EnsemblePredictor (whose methods call these functions)."""
     cases = _check_cases(list_of_data, batch_size)
     out = [None] * len(cases)
     _accumulate_cases(net, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, _logits_sink(out),
@@ -488,9 +486,8 @@ def predict_cases_segmentation(net, list_of_data, patch_size, tile_step_size=0.5
     un-normalised accumulators to its label map in one pass.  properties: None or one dict per case.  Returns a list of uint8 label maps,
     with return_probabilities a list of (seg, probs)."""
     cases = _check_cases(list_of_data, batch_size, properties)
-    dev = next(net.parameters()).device
     out = [None] * len(cases)
-    sink = _segmentation_sink(out, dev, regions_class_order, properties, transpose_backward, return_probabilities)
+    sink = _segmentation_sink(out, regions_class_order, properties, transpose_backward, return_probabilities)
     _accumulate_cases(net, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight)
     return out
 
@@ -511,7 +508,7 @@ class EnsemblePredictor:
     Every fold of a Dino U-Net carries the same frozen DINOv3 backbone (checkpoint.py stores its fingerprint instead of its tensors), and the
     backbone's layers do not depend on the adapter (DINOv3_Adapter._forward launches it beside the prior module).  So per window batch and
     mirror combination: one backbone pass, the F heads (prior module, interactions, FAPM, decoder) on its layers, the logits summed over the
-    folds, one du_window_accumulate.  The reference re-runs the whole network F times.
+    folds, one du_window_accumulate_cases.  The reference re-runs the whole network F times.
 
     list_of_parameters: full state dicts of `net`, or compact dicts of checkpoint.compact_state_dict (no frozen backbone entries, no
     decoder.encoder.* aliases).  Everything except the backbone is replicated F times and each set is loaded strictly into its replica
@@ -585,97 +582,47 @@ class EnsemblePredictor:
             total = out if total is None else total.add_(out)             # fold 0's logits are a fresh tensor nobody else holds
         return total.contiguous()
 
-    def _forward(self, batch_size, graph):
-        if not graph:
-            return self._eager_forward
+    # the three things _accumulate_cases asks of a predictor (_NetPredictor: the same of a plain network)
+    folds = property(lambda self: len(self.nets))
 
-        def captured(C, ph, pw):
-            key = (batch_size, C, ph, pw)
-            if key not in self._forward_cache:                             # backbone + F heads: one graph per (batch, C, patch)
-                self._forward_cache[key] = _WindowForward(self._eager_forward, (batch_size, C, ph, pw), self.device)
-            return self._forward_cache[key]
+    def _captures(self):
+        return self._forward_cache, ()                                     # backbone + F heads: one graph per (batch, C, patch)
 
-        def graph_forward(xb):
-            return captured(*xb.shape[1:])(xb)
-
-        graph_forward.static_input = lambda C, ph, pw: captured(C, ph, pw).x
-        return graph_forward
-
-    @torch.no_grad()
-    def _accumulate(self, data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes):
-        """_accumulate_windows of the ensemble: the accumulators hold the SUM over the folds; n_predictions is scaled by F so that
-        sums / n_predictions is the mean logit (one (D, H, W) plane, instead of a pass over the K planes)"""
-        assert data.ndim == 4, "input_image must be a 4D tensor (c, d, y, x)"
+    @contextlib.contextmanager
+    def _eval_mode(self):
         modes = _training_flags(self.backbone)
         self.backbone.eval()
         try:
-            pred, npred, slices = _window_loop(self._forward(batch_size, graph), self.device, data, patch_size, tile_step_size,
-                                               use_gaussian, batch_size, mirror_axes)
+            yield
         finally:
             _set_training_flags(modes)
-        if len(self.nets) > 1:
-            npred.mul_(float(len(self.nets)))
-        return pred, npred, slices
 
-    @torch.no_grad()
     def predict_logits(self, data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False, mirror_axes=None):
         """predict_sliding_window_logits of the ensemble: the mean over the folds of the logits (K, D, H, W), fp32 on the GPU"""
-        pred, npred, (ys, xs) = self._accumulate(data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes)
-        _lib.check(_lib.lib().du_window_normalize(pred.data_ptr(), npred.data_ptr(), pred.shape[0], npred.numel(),
-                                                  torch.cuda.current_stream().cuda_stream), "du_window_normalize")
-        if not math.isfinite(float(pred.abs().max())):
-            raise RuntimeError("Encountered inf in predicted array")                             # :612-615
-        return pred[:, :, ys, xs]
+        return predict_sliding_window_logits(self, data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes)
 
-    @torch.no_grad()
     def predict_segmentation(self, data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False, mirror_axes=None, *,
                              regions_class_order=None, properties=None, transpose_backward=None, return_probabilities=False):
         """export.predict_segmentation of the ensemble: the window loop, then ONE pass from the accumulators to the label map.  The positive
         factor 1 / F cannot change a label, so without resampling the sums over folds and windows decide."""
-        from . import export
-        pred, npred, (ys, xs) = self._accumulate(data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes)
-        window = (ys.start, xs.start, ys.stop - ys.start, xs.stop - xs.start)
-        return export._export(pred, npred, window, regions_class_order, properties, transpose_backward, return_probabilities)
+        return predict_segmentation(self, data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes,
+                                    regions_class_order=regions_class_order, properties=properties, transpose_backward=transpose_backward,
+                                    return_probabilities=return_probabilities)
 
-    @torch.no_grad()
-    def _accumulate_cases(self, cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight):
-        """_accumulate for a list of cases (_window_loop_cases): every case's n_predictions is scaled by F before `sink` sees it"""
-        folds = float(len(self.nets))
-
-        def scaled(group):
-            if folds > 1:
-                for _, _, npred, _ in group:
-                    npred.mul_(folds)
-            sink(group)
-
-        modes = _training_flags(self.backbone)
-        self.backbone.eval()
-        try:
-            _window_loop_cases(self._forward(batch_size, graph), self.device, cases, patch_size, tile_step_size, use_gaussian, batch_size,
-                               mirror_axes, scaled, full_batch=graph, max_voxels_in_flight=max_voxels_in_flight)
-        finally:
-            _set_training_flags(modes)
-
-    @torch.no_grad()
     def predict_cases_logits(self, list_of_data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
                              mirror_axes=None, *, max_voxels_in_flight=2 ** 26):
         """predict_cases_logits of the ensemble: per case the mean over the folds of the logits (K, D, H, W), fp32 on the GPU"""
-        cases = _check_cases(list_of_data, batch_size)
-        out = [None] * len(cases)
-        self._accumulate_cases(cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, _logits_sink(out),
-                               max_voxels_in_flight)
-        return out
+        return predict_cases_logits(self, list_of_data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes,
+                                    max_voxels_in_flight=max_voxels_in_flight)
 
-    @torch.no_grad()
     def predict_cases_segmentation(self, list_of_data, patch_size, tile_step_size=0.5, use_gaussian=True, batch_size=8, graph=False,
                                    mirror_axes=None, *, regions_class_order=None, properties=None, transpose_backward=None,
                                    return_probabilities=False, max_voxels_in_flight=2 ** 26):
         """predict_cases_segmentation of the ensemble: a list of label maps (or of (seg, probs))"""
-        cases = _check_cases(list_of_data, batch_size, properties)
-        out = [None] * len(cases)
-        sink = _segmentation_sink(out, self.device, regions_class_order, properties, transpose_backward, return_probabilities)
-        self._accumulate_cases(cases, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes, sink, max_voxels_in_flight)
-        return out
+        return predict_cases_segmentation(self, list_of_data, patch_size, tile_step_size, use_gaussian, batch_size, graph, mirror_axes,
+                                          regions_class_order=regions_class_order, properties=properties,
+                                          transpose_backward=transpose_backward, return_probabilities=return_probabilities,
+                                          max_voxels_in_flight=max_voxels_in_flight)
 
     def predict_from_raw(self, data, properties, patch_size, **kwargs):
         """preprocessing.predict_from_raw with this ensemble in place of one network: raw array in, ensemble label map out"""
@@ -729,9 +676,6 @@ def predict_from_list_of_npy_arrays(net_or_predictor, image_or_list_of_images, p
     out, pre, first, voxels = [], [], 0, 0
 
     def flush():
-        if isinstance(net_or_predictor, EnsemblePredictor):
-            return net_or_predictor.predict_cases_segmentation(pre, patch_size, properties=props[first:first + len(pre)],
-                                                               transpose_backward=transpose_backward, **predict_kwargs)
         return predict_cases_segmentation(net_or_predictor, pre, patch_size, properties=props[first:first + len(pre)],
                                           transpose_backward=transpose_backward, **predict_kwargs)
 

@@ -568,6 +568,4 @@ def predict_from_raw(net, data, properties, patch_size, *, transpose_forward, sp
                       use_mask_for_norm=use_mask_for_norm,
                       foreground_intensity_properties_per_channel=foreground_intensity_properties_per_channel)
     transpose_backward = [tf.index(i) for i in range(3)]
-    if isinstance(net, EnsemblePredictor):
-        return net.predict_segmentation(pre, patch_size, properties=properties, transpose_backward=transpose_backward, **predict_kwargs)
     return predict_segmentation(net, pre, patch_size, properties=properties, transpose_backward=transpose_backward, **predict_kwargs)

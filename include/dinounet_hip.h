@@ -670,12 +670,10 @@ int du_debug_attn_census(uint64_t* host, int n);
 
 /* ---- sliding-window inference: predicted_logits[sl] += prediction * gaussian; n_predictions[sl] += gaussian
    (dinounet/inference/predict_from_raw_data.py:607-608) for a batch of nb windows, then predicted_logits /= n_predictions (:610).
-   logits (nb, K, ph, pw) fp32; gauss (ph, pw) fp32; coords (nb, 3) int32 = (slice d, row y0, column x0) of each window;
-   pred (K, D, H, W) and npred (D, H, W) fp32 accumulators, zero-initialised by the caller before the first window. */
-int du_window_accumulate(const float* logits, const float* gauss, const int32_t* coords, float* pred, float* npred, int nb, int K,
-                         int ph, int pw, int D, int H, int W, void* stream);
+   pred (K, D, H, W) and npred (D, H, W) fp32 accumulators, zero-initialised by the caller before the first window; n = D * H * W. */
 int du_window_normalize(float* pred, const float* npred, int K, int64_t n, void* stream);
-/* ... over a LIST of cases, one window batch holding windows of several of them (csrc/window.hip).  All tables are DEVICE arrays:
+/* The accumulation runs over a LIST of cases (a single case is a list of one), one window batch holding windows of several of them
+   (csrc/window.hip).  All tables are DEVICE arrays:
    geom (ncases, 3) int32 = (D, H, W) of each case; desc (nb, 4) int32 on 16 bytes = (case, d, y0, x0) of each window, y0 / x0 in the case's
    padded frame Hp = max(H, ph), lo_y = (Hp - H) / 2, likewise x (pad_nd_image: centred, the odd pixel on the high side).
    du_window_gather: cases = table of ncases pointers to contiguous fp32 (C, D, H, W) volumes; x (slots, C, ph, pw) fp32 = the windows, a source
@@ -694,7 +692,7 @@ int du_window_accumulate_cases(const float* logits, const float* gauss, const in
 /* ---- export tail: accumulators -> label map in the case's original geometry, in ONE pass
    (convert_predicted_logits_to_segmentation_with_correct_shape, dinounet/inference/export_prediction.py:15-68, with
    LabelManager.convert_probabilities_to_segmentation / revert_cropping_on_probabilities, utilities/label_handling/label_handling.py:143-175,
-   185-209).  sums (K, D, Hp, Wp) fp32 = the un-normalised predicted_logits of du_window_accumulate, npred (D, Hp, Wp) fp32 (NULL = 1:
+   185-209).  sums (K, D, Hp, Wp) fp32 = the un-normalised predicted_logits of du_window_accumulate_cases, npred (D, Hp, Wp) fp32 (NULL = 1:
    finished logits); (y0, x0, Hc, Wc) the un-padding window inside (Hp, Wp); (Ho, Wo) = shape_after_cropping_and_before_resampling[1:];
    (D0, H0, W0) = shape_before_cropping, (bd, by, bx) the low corner of bbox_used_for_cropping, whose size is (D, Ho, Wo).
    seg (D0, H0, W0) uint8, written in full (0 outside the bbox); probs (K, D0, H0, W0) fp32 or NULL (outside the bbox: plane 0 = 1 in softmax

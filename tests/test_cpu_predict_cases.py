@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from dinounet_amd import inference as INF
+from _window_ref import plain_accumulate
 
 # list A of the issue: patch (64, 64), step 0.5, batch 8 -> 1, 1, 6, 4, 3, 4 windows = 19 windows in 3 chunks (the per-case loop: 6)
 LIST_A = [(1, 40, 50), (1, 64, 64), (1, 70, 100), (1, 96, 96), (3, 64, 64), (1, 130, 64)]
@@ -69,6 +70,13 @@ def test_plan_case_larger_than_the_budget_is_its_own_group():
 CASES = [(1, 5, 7), (2, 8, 12), (1, 13, 12), (3, 9, 31)]
 
 
+def test_plan_chunks_above_the_accumulate_launch_limit():
+    """the chunks tests/test_gpu_predict_cases.py accumulates in two launches (MAX_WINDOW_BATCH slots, then the rest)"""
+    assert INF.MAX_WINDOW_BATCH == 64
+    assert [[len(c) for c in chunks] for _, chunks in INF.plan_case_batches([CASES[3]], (6, 10), 0.3, 128)] == [[72]]
+    assert [[len(c) for c in chunks] for _, chunks in INF.plan_case_batches(CASES, (6, 10), 0.3, 100)] == [[95]]
+
+
 def make_cases(C, seed=0):
     rng = np.random.default_rng(seed)
     return [rng.standard_normal((C, *s)).astype(np.float32) for s in CASES]
@@ -80,13 +88,6 @@ def plain_gather(cases, desc, patch, slots):
         p, _ = INF.pad_to_patch(torch.from_numpy(cases[i]), patch)
         out[s] = p[:, d, y0:y0 + patch[0], x0:x0 + patch[1]]
     return out.numpy()
-
-
-def plain_accumulate(logits, gauss, desc, preds, npreds):
-    ph, pw = gauss.shape
-    for b, (i, d, y0, x0) in enumerate(desc):                                      # predict_from_raw_data.py:607-608, float32
-        preds[i][:, d, y0:y0 + ph, x0:x0 + pw] += logits[b] * gauss
-        npreds[i][d, y0:y0 + ph, x0:x0 + pw] += gauss
 
 
 @pytest.mark.parametrize("patch", [(8, 12), (6, 10)])

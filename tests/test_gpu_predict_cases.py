@@ -1,11 +1,14 @@
-"""GPU tests (-m gpu) of the cases path of inference: du_window_gather and du_window_accumulate_cases (csrc/window.hip) to the bit against
-the torch construction / the host restatement, _window_loop_cases against _window_loop where both are exact, the loop with a stand-in
-forward (forward counts, independence of the list's order), and predict_cases_segmentation / predict_from_list_of_npy_arrays against the
-single-case functions on a real network.
+"""GPU tests (-m gpu) of the window loop of inference: du_window_gather and du_window_accumulate_cases (csrc/window.hip) to the bit against
+the torch construction / the host restatement, _window_loop_cases to the bit against the plain construction (tests/_window_ref.py: padded
+copy, slices, the sequential `+=`), the loop with a stand-in forward (forward counts, independence of the list's order, chunks above the
+64 slots of a launch), the single-case functions as the list of one, and predict_cases_segmentation / predict_from_list_of_npy_arrays
+against the single-case functions on a real network.
 
 Bounds.  Kernels: bit for bit, no tolerance (a copy; a fixed order of fp32 operations).  End to end: the label maps of two runs whose fp32
 summation order differs agree outside the tie band of tests/test_gpu_export.py (float64 top-two gap below 1e-5 * max|logit|) and the
 share of differing voxels is below 1e-4, that file's bound."""
+from functools import partial
+
 import numpy as np
 import pytest
 import torch
@@ -14,6 +17,7 @@ from dinounet_amd import _lib
 from dinounet_amd import export as EX
 from dinounet_amd import inference as INF
 from test_gpu_ops import dev, gen
+from _window_ref import plain_accumulate, plain_window_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -164,19 +168,39 @@ def integer_forward(calls=None):
     return forward
 
 
+def pointwise_forward(x):
+    """PointwiseNet's arithmetic as a function: non-integer logits that do not depend on the batch a window sits in"""
+    return torch.stack([torch.tanh(x[:, 0]) * 0.75 + x[:, 1], x[:, 0] * x[:, 1] - 1.25], 1).contiguous()
+
+
+def importance_map(patch, use_gaussian):
+    """the loop's weights, float32 on the host"""
+    return INF.compute_gaussian(patch, sigma_scale=1.0 / 8, value_scaling_factor=10) if use_gaussian else torch.ones(patch)
+
+
+def loop_accumulators(forward, d, cases, patch, step, use_gaussian, batch_size, mirror=None):
+    """{case index: (pred, npred, (y slice, x slice))}: what _window_loop_cases hands to its sink"""
+    got = {}
+    INF._window_loop_cases(forward, d, cases, patch, step, use_gaussian, batch_size, mirror, lambda group: got.update({g[0]: g[1:] for g in group}))
+    assert sorted(got) == list(range(len(cases)))
+    return got
+
+
 @pytest.mark.parametrize("mirror", [None, (0, 1)])
 def test_old_and_new_loop_agree_where_both_are_exact(mirror):
-    """use_gaussian=False and integer logits: every fp32 sum is exact whatever its order (the old loop's atomics included); with both mirror
-    axes the averages are multiples of 1/4 below 2^8, still exact"""
+    """The loop against the plain construction (padded copy, slices, the sequential fp32 `+=`), to the bit.  use_gaussian=False and integer
+    logits: every fp32 sum is exact whatever its order; with both mirror axes the averages are multiples of 1/4 below 2^8, still exact.
+    The reference being the sequential loop, the order is pinned too: the Gaussian and non-integer logits, to the bit as well."""
     d, patch = dev(), (8, 12)
     cases = [gen(2, *s, seed=20 + i).to(d) for i, s in enumerate(CASES)]
-    got = {}
-    INF._window_loop_cases(integer_forward(), d, cases, patch, 0.5, False, 5, mirror, lambda group: got.update({g[0]: g[1:] for g in group}))
-    assert sorted(got) == [0, 1, 2, 3]
-    for i, c in enumerate(cases):
-        pred, npred, (ys, xs) = INF._window_loop(integer_forward(), d, c, patch, 0.5, False, 5, mirror)
-        assert same_bits(got[i][0], pred) and same_bits(got[i][1], npred) and got[i][2] == (ys, xs)
-    assert float(got[3][1].max()) >= 4.0                                           # windows do meet: the counts are the weights here
+    for use_gaussian, forward in ((False, integer_forward()), (True, pointwise_forward)):
+        got = loop_accumulators(forward, d, cases, patch, 0.5, use_gaussian, 5, mirror)
+        gauss = importance_map(patch, use_gaussian).numpy()
+        for i, c in enumerate(cases):
+            pred, npred, (ys, xs) = plain_window_sums(forward, c, patch, 0.5, gauss, 5, mirror)
+            assert same_bits(got[i][0], torch.from_numpy(pred)) and same_bits(got[i][1], torch.from_numpy(npred)) and got[i][2] == (ys, xs)
+        if not use_gaussian:
+            assert float(got[3][1].max()) >= 4.0                                   # windows do meet: the counts are the weights here
 
 
 class PointwiseNet(torch.nn.Module):
@@ -210,10 +234,9 @@ def test_loop_with_a_stand_in_forward():
         one, = INF.predict_cases_logits(net, [c], (64, 64), **kw)
         assert same_bits(out[i], rev[i]) and same_bits(out[i], one)
     assert len(net.calls) == 6                                                     # what the per-case loop pays
-    # ... and the values are those of the single-case function (whose atomics may order 3+ meeting windows differently: fp32 round-off)
+    # ... and the values are those of the single-case function
     for i in (2, 5):
-        want = INF.predict_sliding_window_logits(net, cases[i], (64, 64), **kw)
-        assert float((out[i] - want).abs().max()) <= 1e-5 * float(want.abs().max())
+        assert same_bits(out[i], INF.predict_sliding_window_logits(net, cases[i], (64, 64), **kw))
     # a small budget: more groups, the same bits
     split = INF.predict_cases_logits(net, cases, (64, 64), max_voxels_in_flight=22000, **kw)
     assert all(same_bits(a, b) for a, b in zip(split, out))
@@ -235,6 +258,79 @@ def test_non_finite_names_the_cases():
         INF.predict_cases_segmentation(net, cases, (64, 64), batch_size=8)
     cases[2][1, 0, 3, 4] = 0.0
     assert len(INF.predict_cases_segmentation(net, cases, (64, 64), batch_size=8)) == 4
+
+
+def test_non_finite_single_case_has_no_case_list():
+    d = dev()
+    net = OverflowNet().to(d)
+    data = gen(2, *LIST_A[2], seed=52).to(d)
+    data[1, 0, 3, 4] = 1e20
+    for predict in (INF.predict_sliding_window_logits, INF.predict_segmentation):
+        with pytest.raises(RuntimeError, match=r"^Encountered inf in predicted array$"):
+            predict(net, data, (64, 64), batch_size=8)
+
+
+class RaisingNet(PointwiseNet):
+    def forward(self, x):
+        raise ValueError("the forward failed")
+
+
+def test_training_flag_restored_when_the_forward_raises():
+    d = dev()
+    net = RaisingNet().to(d)
+    data = gen(2, *LIST_A[0], seed=53).to(d)
+    calls = [lambda: INF.predict_sliding_window_logits(net, data, (64, 64)), lambda: INF.predict_segmentation(net, data, (64, 64)),
+             lambda: INF.predict_cases_logits(net, [data], (64, 64)), lambda: INF.predict_cases_segmentation(net, [data], (64, 64))]
+    for training in (True, False):
+        net.train(training)
+        for call in calls:
+            with pytest.raises(ValueError, match="the forward failed"):
+                call()
+            assert net.training is training
+
+
+# ------------------------------------------------------------------------------------------------ chunks above the 64 slots of an accumulate launch
+def normalized(pred, npred, d):
+    """host sums -> logits on the device by the package's own normalisation (du_window_normalize: the accumulation is what is compared)"""
+    p, n = torch.from_numpy(pred).to(d), torch.from_numpy(npred).to(d)
+    assert _lib.lib().du_window_normalize(p.data_ptr(), n.data_ptr(), p.shape[0], n.numel(), stream()) == 0
+    return p
+
+
+def test_single_case_window_batch_above_the_launch_limit():
+    """batch_size=128 on a case of 72 windows: one forward, the accumulate in launches of 64 + 8 slots"""
+    d, patch = dev(), (6, 10)
+    net = PointwiseNet().to(d)
+    data = gen(2, *CASES[3], seed=70).to(d)
+    assert [[len(c) for c in chunks] for _, chunks in INF.plan_case_batches([CASES[3]], patch, 0.3, 128)] == [[72]]
+    big = INF.predict_sliding_window_logits(net, data, patch, tile_step_size=0.3, batch_size=128)
+    assert net.calls == [72]
+    assert same_bits(big, INF.predict_sliding_window_logits(net, data, patch, tile_step_size=0.3, batch_size=5))
+    with torch.no_grad():
+        pred, npred, (ys, xs) = plain_window_sums(net, data, patch, 0.3, importance_map(patch, True).numpy(), 72)
+    assert same_bits(big, normalized(pred, npred, d)[:, :, ys, xs])
+
+
+def test_loop_chunk_above_the_launch_limit():
+    """one chunk of 95 windows of four cases: launches of 64 + 31 slots, against the host restatement applied to the same split and against
+    the plain loop over all 95"""
+    d, patch = dev(), (6, 10)
+    cases = [gen(2, *s, seed=80 + i).to(d) for i, s in enumerate(CASES)]
+    (_, (chunk,)), = INF.plan_case_batches(CASES, patch, 0.3, 100)
+    assert len(chunk) == 95
+    got = loop_accumulators(pointwise_forward, d, cases, patch, 0.3, True, 100)
+    gauss = importance_map(patch, True).numpy()
+    x = torch.stack([INF.pad_to_patch(cases[i], patch)[0][:, dd, y0:y0 + patch[0], x0:x0 + patch[1]] for i, dd, y0, x0 in chunk])
+    logits = pointwise_forward(x).cpu().numpy()
+    pshapes = [padded(s, patch) for s in CASES]
+    split = [np.zeros((2, *s), np.float32) for s in pshapes], [np.zeros(s, np.float32) for s in pshapes]
+    plain = [np.zeros((2, *s), np.float32) for s in pshapes], [np.zeros(s, np.float32) for s in pshapes]
+    for s0 in range(0, len(chunk), INF.MAX_WINDOW_BATCH):
+        INF._accumulate_cases_numpy(logits[s0:s0 + INF.MAX_WINDOW_BATCH], gauss, chunk[s0:s0 + INF.MAX_WINDOW_BATCH], *split)
+    plain_accumulate(logits, gauss, chunk, *plain)
+    for i in range(len(CASES)):
+        for want_p, want_n in (split, plain):
+            assert same_bits(got[i][0], torch.from_numpy(want_p[i])) and same_bits(got[i][1], torch.from_numpy(want_n[i]))
 
 
 # ------------------------------------------------------------------------------------------------ end to end with the network
@@ -347,6 +443,27 @@ def test_predict_cases_segmentation_end_to_end(who, graph, resample):
         (seg, probs), = pairs
         assert tuple(probs.shape) == (3, *E2E_SHAPES[0][1:])
         assert_same_up_to_band(seg, want[0][0], want[0][1])                        # (another batch composition: the forward's own round-off)
+
+
+@pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
+@pytest.mark.parametrize("who", ["stand-in", "ensemble"])
+def test_single_case_is_the_list_of_one(who, graph):
+    """predict_sliding_window_logits / predict_segmentation (EnsemblePredictor: predict_logits / predict_segmentation) equal element 0 of the
+    predict_cases_* call on [data], to the bit"""
+    if who == "stand-in":
+        net = PointwiseNet().to(dev())
+        data, patch, kw = gen(2, *LIST_A[2], seed=90), (64, 64), dict(tile_step_size=0.5, use_gaussian=True, batch_size=4)   # 6 windows: 4 + 2
+        one_logits, one_seg = partial(INF.predict_sliding_window_logits, net), partial(INF.predict_segmentation, net)
+        list_logits, list_seg = partial(INF.predict_cases_logits, net), partial(INF.predict_cases_segmentation, net)
+    else:
+        p = e2e_predictor()
+        data, patch, kw = e2e_data()[0], (128, 128), E2E_KW
+        one_logits, one_seg, list_logits, list_seg = p.predict_logits, p.predict_segmentation, p.predict_cases_logits, p.predict_cases_segmentation
+    logits = one_logits(data, patch, graph=graph, **kw)
+    assert logits.is_cuda and logits.dtype == torch.float32 and tuple(logits.shape[1:]) == tuple(data.shape[1:])
+    assert same_bits(logits, list_logits([data], patch, graph=graph, **kw)[0])
+    seg = one_seg(data, patch, graph=graph, **kw)
+    assert seg.dtype == torch.uint8 and torch.equal(seg, list_seg([data], patch, graph=graph, **kw)[0])
 
 
 # ------------------------------------------------------------------------------------------------ raw in, labels out
