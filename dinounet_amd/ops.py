@@ -20,7 +20,7 @@ from ._lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SWIGLU, DU_BF16,
 
 __all__ = ["mm", "linear", "conv2d", "conv_transpose2x2", "norm_act", "layer_norm", "msda", "dwconv3x3",
            "maxpool3x3s2", "bilinear_add", "bilinear_resize", "squeeze_excite", "dice_ce_loss", "dice_ce_masked_loss", "dice_bce_loss",
-           "labels_to_regions", "val_dice_ce", "val_dice_bce", "ds_seg_loss", "downsample_seg"]
+           "labels_to_regions", "val_dice_ce", "val_dice_bce", "ds_seg_loss", "downsample_seg", "topk_ce_loss", "dice_topk_loss"]
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -2462,6 +2462,79 @@ def dice_ce_masked_loss(logits, target, ignore_label, smooth=1e-5, group=None):
     """logits (B,K,H,W) fp32, target (B,1,H,W) integer labels in [0,K) or ignore_label -> scalar loss (masked CE - mean masked soft dice)."""
     _req(logits, target)
     return _DiceCEMasked.apply(logits, target, ignore_label, smooth, group)
+
+
+class _TopKLoss(torch.autograd.Function):
+    """TopKLoss (robust_ce_loss.py:19-32) and, with `dice`, DC_and_topk_loss (compound_losses.py:102-150; SoftDiceLoss with softmax,
+    batch_dice, do_bg=False, masked by the ignore label) on fp32 NCHW logits, fused (csrc/loss_topk.hip): per-voxel CE into a values
+    buffer, a radix select of the k_vox-th largest on the device (k_vox depends on the shape only: no read-back, capturable), a uint8
+    selection map with ties broken by the lowest flat index, one backward pass that reads the map.  The top-k is local to the rank; with
+    a process group the Dice sums are all-reduced as in _DiceCEMasked.  Returns (loss, values (B, HW), selection (B, HW), threshold)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, k_vox, ignore_label, dice, smooth, group):
+        logits = logits.float().contiguous()
+        B, K, H, W = logits.shape
+        HW = H * W
+        tgt = target.reshape(B, HW)
+        if tgt.dtype != torch.int64:
+            tgt = tgt.long()
+        tgt = tgt.contiguous()
+        L = _lib.lib()
+        n = int(L.du_topk_loss_ws_elems(B, K, HW))
+        if n <= 0:
+            raise RuntimeError(f"dinounet_hip: the fused top-k loss supports 2..8 classes and fewer than 2^31 voxels, got {K} classes, "
+                               f"{B * HW} voxels")
+        dev = logits.device
+        has_ign, ign = (0, 0) if ignore_label is None else (1, int(ignore_label))
+        ws = torch.empty(n, dtype=torch.int32, device=dev)
+        values = torch.empty((B, HW), dtype=torch.float32, device=dev)
+        sums = torch.empty(2 + 3 * (K - 1), dtype=torch.float32, device=dev)
+        _lib.check(L.du_topk_loss_fwd(_p(logits), _p(tgt), _p(values), _p(sums), B, K, HW, has_ign, ign, int(k_vox), _p(ws), n, _st()),
+                   "du_topk_loss_fwd")
+        mult = _dice_group(sums, group, "dice_sums") if dice else 1.0
+        sel = torch.empty((B, HW), dtype=torch.uint8, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        coef = torch.empty(2 * (K - 1) + 1, dtype=torch.float32, device=dev)
+        info = torch.empty(4, dtype=torch.int32, device=dev)
+        _lib.check(L.du_topk_loss_finish(_p(sums), _p(values), _p(ws), n, _p(sel), _p(loss), _p(coef), _p(info), B, K, HW, int(k_vox),
+                                         1 if dice else 0, float(smooth), mult, _st()), "du_topk_loss_finish")
+        ctx.save_for_backward(logits, tgt, sel, coef)
+        ctx.ignore = (has_ign, ign)
+        thr = info[:1].view(torch.float32).view(())
+        ctx.mark_non_differentiable(values, sel, thr)
+        return loss.view(()), values, sel, thr
+
+    @staticmethod
+    def backward(ctx, go, *_):
+        logits, tgt, sel, coef = ctx.saved_tensors
+        B, K, H, W = logits.shape
+        dl = torch.empty_like(logits)
+        gof = go.float().contiguous()
+        _lib.check(_lib.lib().du_topk_loss_bwd(_p(logits), _p(tgt), _p(sel), _p(coef), _p(gof), _p(dl), B, K, H * W, ctx.ignore[0],
+                                               ctx.ignore[1], _st()), "du_topk_loss_bwd")
+        return dl, None, None, None, None, None, None
+
+
+def _topk_loss(logits, target, k_percent, ignore_label, dice, smooth, group, return_aux):
+    _req(logits, target)
+    from .training import topk_voxels
+    k_vox = topk_voxels(logits.shape[0] * logits.shape[2] * logits.shape[3], k_percent)
+    loss, values, sel, thr = _TopKLoss.apply(logits, target, k_vox, ignore_label, dice, smooth, group)
+    return (loss, values, sel, thr) if return_aux else loss
+
+
+def topk_ce_loss(logits, target, k_percent, ignore_label=None, return_aux=False):
+    """TopKLoss: logits (B,K,H,W) fp32, target (B,1,H,W) integer labels in [0,K) or ignore_label -> the mean of the
+    int(N k_percent / 100) largest per-voxel cross-entropies (N = B H W; an ignored voxel has CE 0 and counts in N).  return_aux:
+    (loss, values (B, HW) fp32, selection (B, HW) uint8, threshold = the k-th largest value)."""
+    return _topk_loss(logits, target, k_percent, ignore_label, False, 1e-5, None, return_aux)
+
+
+def dice_topk_loss(logits, target, k_percent, ignore_label=None, smooth=1e-5, group=None, return_aux=False):
+    """DC_and_topk_loss: topk_ce_loss - mean soft Dice over classes 1..K-1 (masked by the ignore label; with a group the Dice sums are
+    global, the top-k stays local to the rank).  return_aux as topk_ce_loss."""
+    return _topk_loss(logits, target, k_percent, ignore_label, True, smooth, group, return_aux)
 
 
 class _DiceBCE(torch.autograd.Function):

@@ -112,6 +112,88 @@ def _dc_and_ce_masked(logits, target, ignore_label, smooth=1e-5, ddp=None, group
     return ce - _global_dice((p * onehot).sum((2, 3)), p.sum((2, 3)), sum_gt, smooth, ddp, group)
 
 
+def check_topk_percent(k):
+    """ValueError unless k is a percentage in (0, 100] (any such k is valid: whether it selects a voxel depends on the shape)"""
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or not 0 < k <= 100:
+        raise ValueError(f"top-k loss: k must be a percentage in (0, 100], got {k!r}")
+
+
+def topk_voxels(n_voxels, k):
+    """k_vox of TopKLoss (robust_ce_loss.py:30-31), in its arithmetic: int(np.int64(N) * k / 100), N counting ignored voxels too.
+    ValueError for k outside (0, 100] and for k_vox < 1 -- the reference takes the mean of an empty topk there and returns nan."""
+    import numpy as np
+    check_topk_percent(k)
+    k_vox = int(np.int64(n_voxels) * k / 100)
+    if k_vox < 1:
+        raise ValueError(f"top-k loss: k = {k} % of {n_voxels} voxels selects none (the reference returns nan here)")
+    return k_vox
+
+
+def _topk_ce_torch(logits, target, k, ignore_label):
+    """TopKLoss (robust_ce_loss.py:19-32) in torch: the CPU / many-class path and the fp64 oracle of the fused kernels.  On the GPU it
+    refuses to be captured: a hipGraph holding torch.topk faulted with an illegal memory access when it was replayed
+    (tools/bench_topk_loss.py, (8, 3, 512, 512), k = 10 %; the runtime's dump named a kernel of torch.topk's sort, why it faults under
+    replay is not known); TrainStep / ValStep then fall back to eager steps with a warning.  The fused route has no such limit."""
+    if logits.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("top-k loss: the torch formula (more than 8 classes, or 2^31 voxels and more) cannot be captured into a "
+                           "hipGraph; run eager steps")
+    v = F.cross_entropy(logits, target[:, 0].long(), reduction="none", ignore_index=-100 if ignore_label is None else ignore_label)
+    return torch.topk(v.reshape(-1), topk_voxels(v.numel(), k), sorted=False)[0].mean()
+
+
+def _soft_dice_torch(logits, target, ignore_label, smooth, ddp, group):
+    """SoftDiceLoss(softmax, batch_dice=True, do_bg=False, smooth) as DC_and_topk_loss calls it (compound_losses.py:131-145): with an
+    ignore label the probabilities and the one-hot target are multiplied by m = [t != ignore]; 2tp + fp + fn = P_c + G_c"""
+    lab = target[:, 0].long()
+    prob = torch.softmax(logits, 1)
+    if ignore_label is not None:
+        m = lab != ignore_label
+        lab = torch.where(m, lab, torch.zeros_like(lab))
+        mf = m[:, None].to(logits.dtype)
+    with torch.no_grad():
+        onehot = torch.zeros(prob.shape, device=prob.device, dtype=prob.dtype).scatter_(1, lab[:, None], 1)[:, 1:]
+        if ignore_label is not None:
+            onehot = onehot * mf
+        sum_gt = onehot.sum((2, 3))
+    p = prob[:, 1:] if ignore_label is None else prob[:, 1:] * mf
+    return _global_dice((p * onehot).sum((2, 3)), p.sum((2, 3)), sum_gt, smooth, ddp, group)
+
+
+def topk_fused(is_cuda, num_classes, n_voxels):
+    """the limits of the fused top-k kernels (csrc/loss_topk.hip): a GPU tensor, 2..8 classes, fewer than 2^31 voxels; beyond them the
+    torch formula runs"""
+    return bool(is_cuda) and 2 <= num_classes <= 8 and n_voxels < 2 ** 31
+
+
+def _topk_fused(logits):
+    return topk_fused(logits.is_cuda, logits.shape[1], logits.shape[0] * logits.shape[2] * logits.shape[3])
+
+
+def topk_ce_loss(logits, target, k=10, ignore_label=None):
+    """TopKLoss(k, ignore_index) (robust_ce_loss.py:19-32): the mean of the k_vox = int(N k / 100) largest per-voxel cross-entropies,
+    N = B H W; an ignored voxel has CE 0 and counts in N.  target (B,1,H,W) integer labels.  ValueError where the reference returns nan
+    (k_vox < 1) and for k outside (0, 100].  On the GPU (2..8 classes, N < 2^31) the fused HIP loss (ops.topk_ce_loss, csrc/loss_topk.hip: radix
+    select on the device, ties to the lowest flat index); otherwise torch.topk."""
+    if _topk_fused(logits):
+        from . import ops
+        return ops.topk_ce_loss(logits, target, k, ignore_label)
+    return _topk_ce_torch(logits, target, k, ignore_label)
+
+
+def dc_and_topk_loss(logits, target, k=10, smooth=1e-5, ddp=None, group=None, ignore_label=None):
+    """DC_and_topk_loss (compound_losses.py:102-150; upstream's "Dice + TopK10"), weight_ce = weight_dice = 1: topk_ce_loss + SoftDiceLoss
+    (softmax, batch_dice=True, do_bg=False, smooth; masked by the ignore label).  The reference's host-side `num_fg > 0` test needs no
+    decision here: with every voxel ignored every CE is 0 and so is the top-k mean.  Under DDP the top-k is local to the rank (its own N
+    and k_vox), only the Dice sums are global.  On the GPU (2..8 classes, N < 2^31) the fused HIP loss (ops.dice_topk_loss); the torch formula
+    below is the CPU / many-class path and the fp64 oracle of the tests."""
+    if ddp is None:
+        ddp = _ddp_default(group)
+    if _topk_fused(logits):
+        from . import ops
+        return ops.dice_topk_loss(logits, target, k, ignore_label, smooth, (group if group is not None else dist.group.WORLD) if ddp else None)
+    return _topk_ce_torch(logits, target, k, ignore_label) - _soft_dice_torch(logits, target, ignore_label, smooth, ddp, group)
+
+
 def dc_and_bce_loss(logits, target, use_ignore_label=False, smooth=1e-5, ddp=None, group=None):
     """DC_and_BCE_loss (compound_losses.py:59-99) with MemoryEfficientSoftDiceLoss(sigmoid, batch_dice=True, do_bg=True, smooth=1e-5)
     (nnUNetTrainer.py:356-361): region-based training.  logits (B,R,H,W); target the reference's one-hot form (B, R + u, H, W) in {0,1},
@@ -185,12 +267,18 @@ def labels_to_regions(seg, regions, ignore_label=None, table=None):
 class SegLoss(torch.nn.Module):
     """What nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365) returns for 2D, batch Dice, before the deep-supervision wrapper
     (DeepSupervisionLoss below adds it): DC_and_CE_loss (plain
-    labels or with an ignore label) or DC_and_BCE_loss (regions, with or without an ignore label).  Called as loss(logits, target) with
+    labels or with an ignore label) or DC_and_BCE_loss (regions, with or without an ignore label); with `topk_percent` DC_and_topk_loss
+    (compound_losses.py:102-150, modes "topk" / "topk_ignore"; not with regions).  Called as loss(logits, target) with
     integer label maps (B,1,H,W) in both modes; in region mode the labels become the one-hot region target on the device inside the same
     step (labels_to_regions with the table built here, at construction, outside any capture)."""
 
-    def __init__(self, num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None):
+    def __init__(self, num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None, topk_percent=None):
         super().__init__()
+        if topk_percent is not None:
+            if regions is not None:
+                raise ValueError("top-k loss with regions: the reference has no such loss (DC_and_topk_loss is softmax-only)")
+            check_topk_percent(topk_percent)                     # the range only: k_vox depends on the shape of each call
+        self.topk_percent = topk_percent
         if ignore_label is not None:
             if isinstance(ignore_label, bool) or not isinstance(ignore_label, int):
                 raise ValueError(f"ignore_label must be an int, got {ignore_label!r}")
@@ -209,8 +297,13 @@ class SegLoss(torch.nn.Module):
             dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
             self.register_buffer("table", _region_table(self.regions, dev), persistent=False)
         self.mode = "regions" if self.regions is not None else ("softmax_ignore" if ignore_label is not None else "softmax")
+        if topk_percent is not None:
+            self.mode = "topk_ignore" if ignore_label is not None else "topk"
 
     def forward(self, logits, target):
+        if self.topk_percent is not None:
+            return dc_and_topk_loss(logits, target, self.topk_percent, self.smooth, ddp=self.ddp, group=self.group,
+                                    ignore_label=self.ignore_label)
         if self.regions is None:
             return dc_and_ce_loss(logits, target, self.smooth, ddp=self.ddp, group=self.group, ignore_label=self.ignore_label)
         table = self.table if self.table.device == target.device else None
@@ -309,6 +402,8 @@ class DeepSupervisionLoss(torch.nn.Module):
 
     def fused(self, outs):
         C_ = outs[0].shape[1]
+        if self.mode in ("topk", "topk_ignore"):       # composed of the fused per-scale top-k losses: every scale has its own N and k_vox
+            return False
         return (all(o.is_cuda for o in outs) and len(outs) <= self.MAX_FUSED_SCALES
                 and ((1 <= C_ <= 8) if self.mode == "regions" else (2 <= C_ <= 8)))
 
@@ -342,13 +437,16 @@ class DeepSupervisionLoss(torch.nn.Module):
                                return_scale_losses=return_scale_losses)
 
 
-def build_loss(num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None, deep_supervision_weights=None):
+def build_loss(num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None, deep_supervision_weights=None,
+               topk_percent=None):
     """nnUNetTrainer._build_loss (nnUNetTrainer.py:355-387) for this package: the loss module for plain labels, labels with an ignore
     label, or regions (each an int or a tuple of ints; num_classes = number of network outputs = len(regions)).  Validated on the host:
     ValueError for an ignore label below num_classes, more than 8 regions, a region label outside 0..63 or an ignore label inside a
     region.  With `deep_supervision_weights` (one per decoder output, e.g. deep_supervision_weights(3)) the module is wrapped in a
-    DeepSupervisionLoss, called as loss(outs, target) on the decoder's list.  Pass the result to TrainStep(loss=...)."""
-    base = SegLoss(num_classes, regions=regions, ignore_label=ignore_label, smooth=smooth, ddp=ddp, group=group)
+    DeepSupervisionLoss, called as loss(outs, target) on the decoder's list.  With `topk_percent` (e.g. 10) the module is
+    DC_and_topk_loss instead of DC_and_CE_loss ("Dice + TopK10"; ValueError together with regions); under deep supervision the wrapper
+    then composes the fused per-scale losses on indexed targets.  Pass the result to TrainStep(loss=...)."""
+    base = SegLoss(num_classes, regions=regions, ignore_label=ignore_label, smooth=smooth, ddp=ddp, group=group, topk_percent=topk_percent)
     if deep_supervision_weights is None:
         return base
     return DeepSupervisionLoss(base, deep_supervision_weights)
@@ -706,6 +804,8 @@ class ValStep:
     mode, regions, ignore label, smooth, ddp and group come from it, the region table was built with it, outside any capture.  With a
     DeepSupervisionLoss and a network that returns a list, the step loss is the module's multi-scale forward value (validation_step :963)
     while the counts come from outs[0] and the full-resolution target (:966-968); with any other loss a list is reduced to outs[0].  With a
+    top-k loss (build_loss(..., topk_percent=...)) the counts come from the same softmax / softmax-ignore counts pass and the step loss is
+    the top-k module's forward value.  With a
     group the Dice sums are all-reduced as in the training forward (the reference's validation loss is the same module); under a
     capture that all-reduce is recorded into the graph, a capture that fails falls back to eager steps with a warning, and the multi-rank
     capture itself has been run on CPU / gloo eager steps only, not on several GPUs."""
@@ -720,6 +820,10 @@ class ValStep:
         self.ddp = None if loss is None else loss.ddp
         self.group = None if loss is None else loss.group
         self.ds_loss = loss if isinstance(loss, DeepSupervisionLoss) else None      # step loss = its multi-scale forward value
+        # a top-k loss: the counts come from the softmax / softmax-ignore counts pass, the step loss is the module's forward value
+        self.topk_loss = None
+        if self.mode in ("topk", "topk_ignore"):
+            self.topk_loss = loss.base if isinstance(loss, DeepSupervisionLoss) else loss
         self.table = None
         if self.regions is not None and device.type == "cuda":
             self.table = loss.table if loss.table.device == device else _region_table(self.regions, device)
@@ -754,6 +858,8 @@ class ValStep:
                                            self.ddp, self.group, counts=self.step_counts, accum=self.counts)
                 if ds_loss is not None:
                     loss = ds_loss
+                elif self.topk_loss is not None:
+                    loss = self.topk_loss(logits, self.tgt).detach()
                 self.loss_sum += loss.double()
         finally:
             self.net.train(was_training)

@@ -39,6 +39,7 @@
  *       <- the ignore-label and region configurations of nnUNetTrainer._build_loss (nnUNetTrainer.py:355-365):
  *          DC_and_CE_loss(ignore_label) (compound_losses.py:31-56), DC_and_BCE_loss (compound_losses.py:83-99),
  *          ConvertSegmentationToRegionsTransform (nnUNetTrainer.py:766-767)
+ *   du_topk_loss_*                <- TopKLoss (training/loss/robust_ce_loss.py:19-32), DC_and_topk_loss (compound_losses.py:102-150)
  *   du_export_seg, du_seg_counts
  *       <- convert_predicted_logits_to_segmentation_with_correct_shape (inference/export_prediction.py:15-68) and
  *          compute_metrics' counts (evaluation/evaluate_predictions.py:75-94, 176-186)
@@ -478,6 +479,25 @@ int du_dice_ce_masked_finish(const float* sums, float* loss, float* coef, int K,
 /* dlogits = grad_out[0] * d loss / d logits; exactly 0 in every channel of an ignored pixel */
 int du_dice_ce_masked_bwd(const float* logits, const int64_t* target, const float* coef, const float* grad_out, float* dlogits, int B,
                           int K, int64_t HW, int64_t ignore_label, void* stream);
+
+/* ---- top-k losses: TopKLoss (training/loss/robust_ce_loss.py:19-32) and DC_and_topk_loss (compound_losses.py:102-150) ---- */
+/* logits (B,K,H,W) fp32, target (B,H*W) int64 in [0,K) or, with has_ignore, ignore_label; K in [2,8] (DU_ERR_UNSUPPORTED otherwise),
+   N = B H W < 2^31, 1 <= k_vox <= N (DU_ERR_BAD_ARG otherwise, before any launch).  v = -log p_t per voxel, +0 where ignored.
+   du_topk_loss_fwd: values (N fp32) = v; sums (2 + 3(K-1) floats) = [sum v, n_valid, (I_c, P_c, G_c) c = 1..K-1], the masked loss's
+   layout (under data parallelism the caller all-reduces sums[2:] only; the top-k is local); the radix select of the k_vox-th largest v
+   and the per-wave sums above it are left in ws (du_topk_loss_ws_elems 4-byte words, 16-byte aligned), which du_topk_loss_finish reads:
+   loss (1 float) = mean of the k_vox largest v, minus mean_c dice_c when dice != 0; coef (2(K-1) + 1) = the Dice backward
+   coefficients (zeros when dice == 0) then 1 / k_vox; sel (N uint8) = 1 on exactly k_vox voxels: every v > T and, among v == T, the
+   lowest flat indices; info (4 int32) = (bits of T, k_vox - #{v > T}, #{v > T}, 0); grad_mult = world size when sums[2:] were
+   all-reduced.  du_topk_loss_bwd: dlogits = grad_out[0] * d loss / d logits with the selection read from sel; exactly 0 in every
+   channel of an ignored voxel.  No float atomics: bit-reproducible. */
+int64_t du_topk_loss_ws_elems(int B, int K, int64_t HW);
+int du_topk_loss_fwd(const float* logits, const int64_t* target, float* values, float* sums, int B, int K, int64_t HW, int has_ignore,
+                     int64_t ignore_label, int64_t k_vox, int32_t* ws, int64_t ws_elems, void* stream);
+int du_topk_loss_finish(const float* sums, const float* values, int32_t* ws, int64_t ws_elems, uint8_t* sel, float* loss, float* coef,
+                        int32_t* info, int B, int K, int64_t HW, int64_t k_vox, int dice, float smooth, float grad_mult, void* stream);
+int du_topk_loss_bwd(const float* logits, const int64_t* target, const uint8_t* sel, const float* coef, const float* grad_out,
+                     float* dlogits, int B, int K, int64_t HW, int has_ignore, int64_t ignore_label, void* stream);
 
 /* ---- trainer loss for regions: DC_and_BCE_loss (training/loss/compound_losses.py:59-99; MemoryEfficientSoftDiceLoss with sigmoid,
         do_bg=True, dice.py:58-119; nnUNetTrainer.py:356-361) ---- */
