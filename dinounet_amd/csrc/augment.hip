@@ -12,7 +12,7 @@
 //   du_aug_spatial      SpatialTransform (rotation, isotropic scale, centre crop) + MirrorTransform folded into one resampling pass;
 //                       labels follow batchgenerators' order-1 rule (per label: bilinear interpolation of its one-hot map >= 0.5 with
 //                       cval -1 outside the image, ascending labels overwrite; pixels no label claims are 0, which is also what
-//                       RemoveLabelTransform(-1, 0) leaves)
+//                       RemoveLabelTransform(-1, 0) leaves; a coordinate outside [0, Hi - 1] x [0, Wi - 1] is cval itself, hence 0)
 //   du_aug_plane_stats  per (sample, channel) plane: mean, std (population), min, max
 //   du_aug_noise_mult   GaussianNoiseTransform (x + N(0, sigma^2), sigma ~ U(0, 0.1) drawn by the host) then BrightnessMultiplicativeTransform (x * m)
 //   du_aug_contrast     ContrastAugmentationTransform, preserve_range: clip((x - mean) * f + mean, min, max)
@@ -25,10 +25,14 @@
 
 namespace {
 
-__device__ __forceinline__ float keys(float t) {          // Keys cubic convolution kernel, a = -0.5
+// Keys cubic convolution kernel, a = -0.5: 1.5 t^3 - 2.5 t^2 + 1 on [0, 1], -0.5 t^3 + 2.5 t^2 - 4 t + 2 on (1, 2), each written with the
+// factor that vanishes at t = 1 / t = 2 taken out.  Those factors are exact differences, so a weight errs relative to itself; in Horner
+// form the small weights next to t = 1 and t = 2 are differences of terms of size 2 to 4 and err by 2^-22 absolute, which shows where a
+// far tap is the only one inside the image.
+__device__ __forceinline__ float keys(float t) {
   t = fabsf(t);
-  if (t <= 1.f) return (1.5f * t - 2.5f) * t * t + 1.f;
-  if (t < 2.f) return ((-0.5f * t + 2.5f) * t - 4.f) * t + 2.f;
+  if (t <= 1.f) return (1.f - t) * ((1.f + t) - 1.5f * t * t);
+  if (t < 2.f) { const float u = 2.f - t; return -0.5f * (t - 1.f) * u * u; }
   return 0.f;
 }
 
@@ -89,35 +93,61 @@ __global__ __launch_bounds__(256) void aug_spatial_kernel(const float* __restric
         for (int j = 0; j < 4; j++) s += (lab[j] == lab[k]) ? w[j] : 0.f;
         if (s >= 0.5f && lab[k] > best) best = lab[k];
       }
-      sout[((long)b * Ho + yo) * Wo + xo] = best;
+      // map_coordinates(mode="constant") does not interpolate towards cval: a coordinate outside [0, Hi - 1] x [0, Wi - 1] IS cval in every
+      // one-hot map, also in the half-pixel strip where the bilinear weight of the in-image neighbours still reaches 1/2
+      const bool inside = y >= 0.f && y <= (float)(Hi - 1) && x >= 0.f && x <= (float)(Wi - 1);
+      sout[((long)b * Ho + yo) * Wo + xo] = inside ? best : 0.f;
     }
   }
 }
 
-// one workgroup per plane: out[p] = (mean, population std, min, max)
+// one workgroup per plane: out[p] = (mean, population std, min, max).  Two passes over the plane (the second comes from L2), so that the
+// statistics of a plane whose mean is far from 0 -- |mean| / std = 100 is ordinary after z-scoring -- err relative to its std, not to its
+// mean: E[x^2] - mean^2 in fp32 loses (mean / std)^2 roundings.  Pass 1 sums x - p[0] (shifted: its terms are of the size of the spread)
+// and takes min / max: m1 = p[0] + sum / n.  Pass 2 sums d = x - m1 and d^2: mean = m1 + c, var = E[d^2] - c^2 with c = E[d], the
+// corrected two-pass formula (c is of the size of m1's rounding).  A constant plane gives d = 0 and std exactly 0.
 __global__ __launch_bounds__(1024) void aug_plane_stats_kernel(const float* __restrict__ x, float* __restrict__ out, long n) {
   __shared__ float red[4][16];
+  __shared__ float m1s;
   const float* p = x + (long)blockIdx.x * n;
-  float s = 0.f, s2 = 0.f, mn = 3.4e38f, mx = -3.4e38f;
+  const float K = p[0];
+  float s = 0.f, mn = 3.4e38f, mx = -3.4e38f;
   for (long i = threadIdx.x * 4L; i < n; i += 4096) {
     const float4 v = *(const float4*)(p + i);
-    s += v.x + v.y + v.z + v.w;
-    s2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    s += (v.x - K) + (v.y - K) + (v.z - K) + (v.w - K);
     mn = fminf(fminf(mn, fminf(v.x, v.y)), fminf(v.z, v.w));
     mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
   }
-  s = wave_sum(s); s2 = wave_sum(s2);
+  s = wave_sum(s);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
   const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][w] = s; red[1][w] = s2; red[2][w] = mn; red[3][w] = mx; }
+  if ((threadIdx.x & 63) == 0) { red[0][w] = s; red[2][w] = mn; red[3][w] = mx; }
+  __syncthreads();
+  float c = 3.4e38f, d = -3.4e38f;
+  if (threadIdx.x == 0) {
+    float a = 0.f;
+    for (int k = 0; k < 16; k++) { a += red[0][k]; c = fminf(c, red[2][k]); d = fmaxf(d, red[3][k]); }
+    m1s = K + a / (float)n;
+  }
+  __syncthreads();
+  const float m1 = m1s;
+  float s1 = 0.f, s2 = 0.f;
+  for (long i = threadIdx.x * 4L; i < n; i += 4096) {
+    const float4 v = *(const float4*)(p + i);
+    const float dx = v.x - m1, dy = v.y - m1, dz = v.z - m1, dw = v.w - m1;
+    s1 += dx + dy + dz + dw;
+    s2 += dx * dx + dy * dy + dz * dz + dw * dw;
+  }
+  s1 = wave_sum(s1); s2 = wave_sum(s2);
+  if ((threadIdx.x & 63) == 0) { red[0][w] = s1; red[1][w] = s2; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float a = 0.f, b = 0.f, c = 3.4e38f, d = -3.4e38f;
-    for (int k = 0; k < 16; k++) { a += red[0][k]; b += red[1][k]; c = fminf(c, red[2][k]); d = fmaxf(d, red[3][k]); }
-    const float mean = a / (float)n;
-    float var = b / (float)n - mean * mean;
-    out[blockIdx.x * 4 + 0] = mean;
+    float a = 0.f, b = 0.f;
+    for (int k = 0; k < 16; k++) { a += red[0][k]; b += red[1][k]; }
+    const float corr = a / (float)n;
+    const float var = b / (float)n - corr * corr;
+    out[blockIdx.x * 4 + 0] = m1 + corr;
     out[blockIdx.x * 4 + 1] = sqrtf(fmaxf(var, 0.f));
     out[blockIdx.x * 4 + 2] = c;
     out[blockIdx.x * 4 + 3] = d;

@@ -603,7 +603,8 @@ int du_pack_weights(const int64_t* table, const int64_t* bprefix, int n, int64_t
    data (B,C,Hi,Wi) -> data_out (B,C,Ho,Wo) bicubic, zero outside; seg (B,1,Hi,Wi) (nullable) -> seg_out by the order-1 label rule. */
 int du_aug_spatial(const float* data, const float* seg, const float* params, float* data_out, float* seg_out, int B, int C, int Hi, int Wi,
                    int Ho, int Wo, void* stream);
-/* stats (planes, 4) = mean, population std, min, max of every plane (n % 4 == 0) */
+/* stats (planes, 4) = mean, population std, min, max of every plane (n % 4 == 0); two passes, mean and std err relative to the
+   plane's spread whatever its offset */
 int du_aug_plane_stats(const float* x, float* stats, int planes, int64_t n, void* stream);
 /* GaussianNoiseTransform + BrightnessMultiplicativeTransform: x = (x + sigma[p] * N(0,1)) * mult[p]   (sigma 0 / mult 1 = off) */
 int du_aug_noise_mult(float* x, const float* sigma, const float* mult, int planes, int64_t n, int seed, void* stream);
