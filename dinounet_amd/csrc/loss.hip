@@ -100,14 +100,14 @@ __global__ __launch_bounds__(256) void dice_ce_partial_kernel(const float* __res
         cnt[2 * K + k] += t == k ? 1 : 0;
       }
     }
-    float se = 0.f;
+    float se = 0.f, xt = mx;
 #pragma unroll
-    for (int k = 0; k < K; k++) { v[k] = __expf(v[k] - mx); se += v[k]; }
+    for (int k = 0; k < K; k++) { if (k == t) xt = v[k]; v[k] = __expf(v[k] - mx); se += v[k]; }
     const float inv = 1.f / se;
+    if (t >= 0 && t < K) acc[0] += softmax_nll(mx, xt, se);     // shared with the COUNTS twin: this is its text
 #pragma unroll
     for (int k = 0; k < K; k++) {
       const float pk = v[k] * inv;
-      if (k == t) acc[0] -= __logf(fmaxf(pk, 1e-38f));
       if (k >= 1) {
         acc[1 + 3 * (k - 1) + 1] += pk;
         if (k == t) { acc[1 + 3 * (k - 1)] += pk; acc[1 + 3 * (k - 1) + 2] += 1.f; }
@@ -200,7 +200,7 @@ int loss_grid(long npix) { long g = (npix + 255) / 256 / 4; if (g < 1) g = 1; if
 }  // namespace
 
 extern "C" int64_t du_dice_ce_ws_elems(int B, int K, int64_t HW) {
-  if (B <= 0 || K < 2 || K > MAXK || HW <= 0) return 0;
+  if (B <= 0 || K < 2 || K > 8 || HW <= 0) return 0;       // what du_dice_ce_sums launches: 0 is the wrapper's "unsupported"
   return (int64_t)loss_grid((long)B * HW) * (1 + 3 * (K - 1));
 }
 
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float
 #pragma unroll
       for (int k = 0; k < K; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
       const float inv = 1.f / se;
-      acc[0] += valid ? (mx + __logf(se)) - xt : 0.f;     // -log p_t = logsumexp - x_t
+      acc[0] += valid ? softmax_nll(mx, xt, se) : 0.f;
       acc[1] += valid ? 1.f : 0.f;
 #pragma unroll
       for (int k = 1; k < K; k++) {
@@ -849,7 +849,7 @@ __global__ __launch_bounds__(256) void ds_partial_kernel(DsTable d, const int64_
 #pragma unroll
         for (int k = 0; k < N; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
         const float inv = 1.f / se;
-        acc[0] += valid ? (mx + __logf(se)) - xt : 0.f;     // -log p_t = logsumexp - x_t
+        acc[0] += valid ? softmax_nll(mx, xt, se) : 0.f;
         acc[1] += valid ? 1.f : 0.f;
 #pragma unroll
         for (int k = 1; k < N; k++) {

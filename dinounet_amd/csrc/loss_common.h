@@ -49,6 +49,12 @@ __device__ __forceinline__ void st4b(uint8_t* __restrict__ p, bool vec, int n, u
   }
 }
 
+// -log p_t of one pixel from the softmax pass: mx = max_k x_k, xt = the target's logit, se = sum_k exp(x_k - mx) in [1, K].  The order is
+// log_softmax's: mx - xt is exact or rounds once at its own size and log se <= log K, so the error does not grow with a common offset
+// of the logits ((mx + log se) - xt rounds at |mx|), and a target far below the maximum gives its gap, not a saturated -log of an
+// underflowed p.  Every softmax body of the loss family goes through this one line.
+__device__ __forceinline__ float softmax_nll(float mx, float xt, float se) { return (mx - xt) + __logf(se); }
+
 template <int NS>
 __device__ __forceinline__ void block_partial_store(float (&acc)[NS], float* __restrict__ part) {
   __shared__ float red[4][NS];

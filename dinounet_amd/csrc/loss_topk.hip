@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void topk_values_kernel(const float* __restric
 #pragma unroll
       for (int k = 0; k < K; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
       const float inv = 1.f / se;
-      const float nll = (mx + __logf(se)) - xt;            // -log p_t = logsumexp - x_t
+      const float nll = softmax_nll(mx, xt, se);
       ce[j] = (valid && nll > 0.f) ? nll : 0.f;            // +0 for an ignored voxel, for -0 and for a nan: the bits order as integers
       acc[0] += ce[j];
       acc[1] += valid ? 1.f : 0.f;

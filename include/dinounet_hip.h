@@ -453,8 +453,9 @@ int du_se_scale_bwd(int dtype, const void* dy, int64_t lddy, const float* gate, 
                     int64_t P, int C, void* stream);
 
 /* ---- trainer loss: DC_and_CE_loss (training/loss/compound_losses.py:8-56, dice.py:58-119: batch dice, no background, smooth 1e-5) ---- */
-/* logits (B,K,H,W) fp32 NCHW, target (B,H*W) int64 labels, K in [2,8].  sums: 1 + 3(K-1) floats = [sum -log p_t, (I_c, P_c, G_c) c>=1].
-   scratch: du_dice_ce_ws_elems floats.  Under data parallelism the caller all-reduces sums[1:] between _sums and _finish. */
+/* logits (B,K,H,W) fp32 NCHW, target (B,H*W) int64 labels, K in [2,8] (K < 2: DU_ERR_BAD_ARG, K > 8:
+   DU_ERR_UNSUPPORTED, before any launch).  sums: 1 + 3(K-1) floats = [sum -log p_t, (I_c, P_c, G_c) c>=1].
+   scratch: du_dice_ce_ws_elems floats (0 for a K outside [2,8]).  Under data parallelism the caller all-reduces sums[1:] between _sums and _finish. */
 int64_t du_dice_ce_ws_elems(int B, int K, int64_t HW);
 int du_dice_ce_sums(const float* logits, const int64_t* target, float* sums, int B, int K, int64_t HW, float* ws, int64_t ws_elems,
                     void* stream);
