@@ -95,6 +95,30 @@ def lib():
     return _lib
 
 
+def upload(arrays, dtype, device):
+    """Small host arrays -> device tensors of their shapes, as views of ONE buffer sent with ONE asynchronous copy from pinned memory.
+    `tensor.to(device)` from pageable memory is a synchronous copy on the current stream: the host would wait for everything queued
+    there (the previous step's graph replay) once per array.  The staging buffer is a fresh pinned tensor each call; torch's caching
+    host allocator records the copy against it and hands the block out again only once the copy has finished, so letting it go here
+    is safe.  Every array starts on a 256-byte boundary of the buffer.  dtype: a numpy dtype torch knows (float32, int32, int64)."""
+    import numpy as np
+    import torch
+    arrays = [np.ascontiguousarray(a, dtype) for a in arrays]
+    per = max(1, 256 // np.dtype(dtype).itemsize)
+    offsets, n = [], 0
+    for a in arrays:
+        offsets.append(n)
+        n += -(-max(a.size, 1) // per) * per
+    flat = np.zeros(n, dtype)
+    for a, o in zip(arrays, offsets):
+        flat[o:o + a.size] = a.reshape(-1)
+    flat = torch.from_numpy(flat)
+    host = torch.empty(n, dtype=flat.dtype, pin_memory=True)
+    host.copy_(flat)
+    buf = host.to(device, non_blocking=True)
+    return [buf[o:o + a.size].view(a.shape) for a, o in zip(arrays, offsets)]
+
+
 def check(rc: int, what: str):
     if rc != 0:
         raise RuntimeError(f"dinounet_hip: {what} failed with {ERRORS.get(rc, rc)}")

@@ -295,23 +295,26 @@ class GPUAugment2D:
         B, Cc, Hi, Wi = data.shape
         H, W = self.patch
         dev = data.device
-        dv = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
         data = data.contiguous().float()
         seg = None if seg is None else seg.contiguous().float()
         out = torch.empty((B, Cc, H, W), dtype=torch.float32, device=dev)
         sout = None if seg is None else torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
         # every parameter array is a named device tensor that outlives its launch (a temporary handed to ctypes as a raw pointer would be
-        # freed -- and its block re-used by the next upload -- before the kernel is even enqueued)
+        # freed -- and its block re-used by the next upload -- before the kernel is even enqueued).  All of them travel in one pinned buffer
+        # with one asynchronous copy (_lib.upload): an upload from pageable memory would make the host wait for the stream, i.e. for the
+        # training step that is still running there
         ones = np.ones((B, Cc), np.float32)
-        t_sp, t_noise, t_one, t_zero = dv(d["spatial"]), dv(d["noise_sigma"]), dv(ones), dv(0 * ones)
-        t_blur, t_mult, t_con, t_zoom = dv(d["blur_sigma"]), dv(d["mult"]), dv(d["contrast"]), dv(d["zoom"])
+        gam_on = {key: (d[key] > 0).astype(np.float32) for key in ("gamma_inv", "gamma")}
+        (t_sp, t_noise, t_one, t_zero, t_blur, t_mult, t_con, t_zoom, t_gi, t_gi_inv, t_gi_on, t_g, t_g_inv, t_g_on) = _lib.upload(
+            [d["spatial"], d["noise_sigma"], ones, 0 * ones, d["blur_sigma"], d["mult"], d["contrast"], d["zoom"],
+             d["gamma_inv"], gam_on["gamma_inv"] * 1.0, gam_on["gamma_inv"], d["gamma"], gam_on["gamma"] * 0.0, gam_on["gamma"]], np.float32, dev)
+        t_gamma = {"gamma_inv": (t_gi, t_gi_inv, t_gi_on.view(-1)), "gamma": (t_g, t_g_inv, t_g_on.view(-1))}
         spline = self.interpolation == "spline"
         if spline:
             if self.mask_channels and self.mask_channels[-1] >= Cc:
                 raise ValueError(f"mask_channels {self.mask_channels} for {Cc} channels")
             if self.mask_channels and seg is None:
                 raise ValueError("mask_channels needs the segmentation: MaskTransform zeroes the channels where the resampled label is negative")
-            di = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
             # coefficients only for the planes of samples that drew a rotation or a scale; the others are cropped
             moved = [b for b in range(B) if not _is_identity(d["spatial"][b])]
             planes = np.array([b * Cc + c for b in moved for c in range(Cc)], np.int32)
@@ -321,7 +324,7 @@ class GPUAugment2D:
             if n_ws < 0:
                 _lib.check(n_ws, "du_aug_spline_ws_elems")
             coef = torch.empty(n_ws, dtype=torch.float64, device=dev)
-            t_planes, t_slots = di(planes if len(planes) else [0]), di(slots)
+            t_planes, t_slots, t_sizes = _lib.upload([planes if len(planes) else [0], slots, _lowres_sizes(d["zoom"], H, W)], np.int32, dev)
             if len(planes):
                 _lib.check(L.du_aug_spline_coeffs(_p(data), B * Cc, _p(t_planes), len(planes), Hi, Wi, _p(coef), n_ws, _st()), "du_aug_spline_coeffs")
             _lib.check(L.du_aug_spatial_spline(_p(data), _p(seg), _p(t_sp), _p(coef), len(planes), _p(t_slots), _p(out), _p(sout), B, Cc, Hi, Wi,
@@ -342,7 +345,6 @@ class GPUAugment2D:
             _lib.check(L.du_aug_contrast(_p(out), _p(t_con), _p(stats), P, n, _st()), "du_aug_contrast")
         if ((d["zoom"] > 0) & (d["zoom"] < 1)).any():
             if spline:
-                t_sizes = di(_lowres_sizes(d["zoom"], H, W))
                 t_bounds = torch.empty((P, 32, 2), dtype=torch.float32, device=dev)
                 t_mid = torch.empty(P * n, dtype=torch.float64, device=dev)
                 _lib.check(L.du_aug_lowres_spline(_p(out), _p(tmp), _p(t_sizes), _p(t_bounds), _p(t_mid), P, H, W, _st()), "du_aug_lowres_spline")
@@ -354,8 +356,7 @@ class GPUAugment2D:
             g = d[key]
             if not (g > 0).any():
                 continue
-            on = (g > 0).astype(np.float32)
-            t_g, t_inv, onv = dv(g), dv(on * inv), dv(on).view(-1)
+            t_g, t_inv, onv = t_gamma[key]                        # gamma, [on] * inv, [on]
             _lib.check(L.du_aug_plane_stats(_p(out), _p(stats), P, n, _st()), "du_aug_plane_stats")       # mean / std to retain, range
             before = stats.clone()
             _lib.check(L.du_aug_gamma(_p(out), _p(t_g), _p(t_inv), _p(stats), P, n, _st()), "du_aug_gamma")

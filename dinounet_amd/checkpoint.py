@@ -37,7 +37,10 @@ def _fingerprint(items):
 
 def _frozen_keys(net):
     """state_dict keys under the backbone whose parameters do not require grad, plus the backbone's buffers (bias_mask, RoPE periods):
-    everything `DINOv3_Adapter` freezes (dinov3_adapter.py:338-341)."""
+    everything `DINOv3_Adapter` freezes (dinov3_adapter.py:338-341).  A network without that backbone has no frozen keys: its compact
+    dict is its state dict."""
+    if getattr(getattr(getattr(net, "encoder", None), "dinov3_adapter", None), "backbone", None) is None:
+        return []
     trainable = {FROZEN_PREFIX + n for n, p in net.encoder.dinov3_adapter.backbone.named_parameters() if p.requires_grad}
     return [k for k in net.state_dict().keys() if k.startswith(FROZEN_PREFIX) and k not in trainable]
 

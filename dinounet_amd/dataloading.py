@@ -352,7 +352,8 @@ class DataLoader2D:
         for j, (data, seg, _) in enumerate(cases):
             jobs[j] = (data.data_ptr(), seg.data_ptr(), data.shape[1], data.shape[2], data.shape[3], d["slices"][j], d["bbox_lbs"][j][0],
                        d["bbox_lbs"][j][1])
-        self._jobs = torch.from_numpy(jobs).to(dev)                                  # stays referenced until the next batch replaces it
+        # (pinned and asynchronous: an upload from pageable memory would make the host wait for the work already queued on the stream)
+        self._jobs = _lib.upload([jobs], np.int64, dev)[0]                           # stays referenced until the next batch replaces it
         out = torch.empty((B, C, ph, pw), dtype=torch.float32, device=dev)
         sout = torch.empty((B, 1, ph, pw), dtype=torch.float32 if seg_float else torch.int16, device=dev)
         _lib.check(_lib.lib().du_dl_gather(self._jobs.data_ptr(), B, C, ph, pw, out.data_ptr(), sout.data_ptr(), int(seg_float), _stream()),
