@@ -204,10 +204,6 @@ extern "C" int64_t du_dice_ce_ws_elems(int B, int K, int64_t HW) {
   return (int64_t)loss_grid((long)B * HW) * (1 + 3 * (K - 1));
 }
 
-#define LOSS_K_SWITCH(K, CALL) \
-  switch (K) { case 2: { CALL(2); break; } case 3: { CALL(3); break; } case 4: { CALL(4); break; } case 5: { CALL(5); break; } \
-               case 6: { CALL(6); break; } case 7: { CALL(7); break; } case 8: { CALL(8); break; } default: return DU_ERR_UNSUPPORTED; }
-
 // sums (1 + 3(K-1)) fp32 <- per-pixel softmax sums of this rank's batch
 extern "C" int du_dice_ce_sums(const float* logits, const int64_t* target, float* sums, int B, int K, int64_t HW, float* ws,
                                int64_t ws_elems, void* stream) {
@@ -217,7 +213,7 @@ extern "C" int du_dice_ce_sums(const float* logits, const int64_t* target, float
   const int NS = 1 + 3 * (K - 1);
   if (ws_elems < (int64_t)grid * NS) return DU_ERR_BAD_ARG;
 #define CALL(KK) hipLaunchKernelGGL((dice_ce_partial_kernel<KK, false>), dim3(grid), dim3(256), 0, st, logits, target, ws, (int*)nullptr, B, (long)HW)
-  LOSS_K_SWITCH(K, CALL)
+  LOSS_SWITCH(K, 2, CALL)
 #undef CALL
   hipLaunchKernelGGL(dice_ce_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid, NS);
   return du_check_launch();
@@ -241,7 +237,7 @@ extern "C" int du_dice_ce_bwd(const float* logits, const int64_t* target, const 
   const long npix = (long)B * HW;
   long g = (npix + 255) / 256; if (g > 8192) g = 8192;
 #define CALL(KK) hipLaunchKernelGGL(dice_ce_bwd_kernel<KK>, dim3((unsigned)g), dim3(256), 0, st, logits, target, coef, grad_out, dlogits, B, (long)HW, 1.f / (float)npix)
-  LOSS_K_SWITCH(K, CALL)
+  LOSS_SWITCH(K, 2, CALL)
 #undef CALL
   return du_check_launch();
 }
@@ -260,27 +256,10 @@ extern "C" int du_dice_ce_bwd(const float* logits, const int64_t* target, const 
 // 2R dice coefficients, so the backward pass needs no host value.  Each lane handles 4 consecutive pixels of one image (16 B per fp32
 // logits plane, one dword per uint8 plane, 32 B of int64 labels); when HW % 4 != 0 the rows are not 16 B aligned and every quad takes
 // the guarded scalar path (the last quad of an image is partial).  Reductions are two-stage, per-block partial rows + one block adding
-// them (partial_rows_sum_kernel): no float atomics, bit-reproducible across calls and graph replays.
+// them (partial_rows_sum_kernel, loss_common.h): no float atomics, bit-reproducible across calls and graph replays.
 namespace {
 
 constexpr int MAXR = 8;
-
-// second stage of the new sums passes: ONE block adds the per-block partial rows (blocks x NS).  Every thread loads all NS columns of its
-// rows at once, so the block waits for one memory round trip instead of NS dependent ones (dice_ce_sum_kernel above walks the columns one
-// at a time, with a strided load and an eight-barrier tree each: ~2 us per column, two thirds of a 512^2 batch-8 sums pass).  Fixed order
-// (rows t, t + 256, ... per thread, DPP wave tree, waves 0..3): bit-reproducible.
-template <int NS>
-__global__ __launch_bounds__(256) void partial_rows_sum_kernel(const float* __restrict__ part, float* __restrict__ sums, int blocks) {
-  float acc[NS];
-#pragma unroll
-  for (int i = 0; i < NS; i++) acc[i] = 0.f;
-  for (int b = threadIdx.x; b < blocks; b += 256) {
-    const float* row = part + (long)b * NS;
-#pragma unroll
-    for (int i = 0; i < NS; i++) acc[i] += row[i];
-  }
-  block_partial_store<NS>(acc, sums);     // gridDim.x == 1: row 0 of `sums`
-}
 
 template <int K, bool COUNTS>
 __global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
@@ -306,9 +285,6 @@ __global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const bool valid = t[j] != ignore;
-      float mx = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < K; k++) mx = fmaxf(mx, v[k][j]);
       if constexpr (COUNTS) {       // an ignored pixel (and the padding of a partial quad) adds to no count
         const int pred = argmax_first<K>([&](int k) { return v[k][j]; });
 #pragma unroll
@@ -318,20 +294,10 @@ __global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float
           cnt[2 * K + k] += (valid && t[j] == k) ? 1 : 0;
         }
       }
-      float e[K], se = 0.f, xt = mx;
+      float x[K];
 #pragma unroll
-      for (int k = 0; k < K; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
-      const float inv = 1.f / se;
-      acc[0] += valid ? softmax_nll(mx, xt, se) : 0.f;
-      acc[1] += valid ? 1.f : 0.f;
-#pragma unroll
-      for (int k = 1; k < K; k++) {
-        const float pk = e[k] * inv;
-        const bool hit = valid && k == t[j];
-        acc[2 + 3 * (k - 1)] += hit ? pk : 0.f;
-        acc[2 + 3 * (k - 1) + 1] += valid ? pk : 0.f;
-        acc[2 + 3 * (k - 1) + 2] += hit ? 1.f : 0.f;
-      }
+      for (int k = 0; k < K; k++) x[k] = v[k][j];
+      softmax_pixel_fwd<K>(x, t[j], valid, acc, [&](float nll) { return valid ? nll : 0.f; });
     }
   }
   block_partial_store<NS>(acc, part);
@@ -342,11 +308,7 @@ __global__ __launch_bounds__(256) void dice_ce_masked_partial_kernel(const float
 __global__ void dice_ce_masked_coef_kernel(const float* __restrict__ sums, float* __restrict__ loss, float* __restrict__ coef, int K,
                                            float smooth, float grad_mult) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const float dc = dice_coefs(sums + 2, coef, K - 1, smooth, grad_mult);
-  const float nv = sums[1];
-  const float ce_scale = nv > 0.f ? 1.f / nv : 0.f;
-  coef[2 * (K - 1)] = ce_scale;
-  loss[0] = sums[0] * ce_scale - dc;
+  loss[0] = loss_finish(sums, sums + 2, coef, K - 1, false, smooth, grad_mult, 1.f);
 }
 
 template <int K>
@@ -354,9 +316,7 @@ __global__ __launch_bounds__(256) void dice_ce_masked_bwd_kernel(const float* __
                                                                  const float* __restrict__ coef, const float* __restrict__ gout,
                                                                  float* __restrict__ dlogits, int B, long HW, int64_t ignore, bool vec) {
   float ca[K], cb[K];
-  ca[0] = 0.f; cb[0] = 0.f;
-#pragma unroll
-  for (int c = 1; c < K; c++) { ca[c] = coef[2 * (c - 1)]; cb[c] = coef[2 * (c - 1) + 1]; }
+  load_dice_coefs<K, K - 1>(coef, ca, cb);
   const float ce_scale = coef[2 * (K - 1)];
   const float go = gout ? gout[0] : 1.f;
   const long nq = (HW + 3) >> 2, items = (long)B * nq;
@@ -372,6 +332,7 @@ __global__ __launch_bounds__(256) void dice_ce_masked_bwd_kernel(const float* __
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const bool valid = t[j] != ignore;
+      const float ce_scale_j = ce_scale;
       float mx = -INFINITY;
 #pragma unroll
       for (int k = 0; k < K; k++) mx = fmaxf(mx, v[k][j]);
@@ -388,22 +349,12 @@ __global__ __launch_bounds__(256) void dice_ce_masked_bwd_kernel(const float* __
       }
 #pragma unroll
       for (int k = 0; k < K; k++)
-        v[k][j] = valid ? go * ((v[k][j] - (k == t[j] ? 1.f : 0.f)) * ce_scale + v[k][j] * (g[k] - dot)) : 0.f;
+        v[k][j] = valid ? go * ((v[k][j] - (k == t[j] ? 1.f : 0.f)) * ce_scale_j + v[k][j] * (g[k] - dot)) : 0.f;
     }
     float* dp = dlogits + b * K * HW + r0;
 #pragma unroll
     for (int k = 0; k < K; k++) st4f(dp + (long)k * HW, vec, n, v[k]);
   }
-}
-
-// sigmoid and the stable BCE-with-logits from one exponential: e = exp(-|x|), bce = max(x, 0) - x y + log(1 + e).  The reciprocal is
-// v_rcp_f32 (1 ulp; 1 + e lies in [1, 2]): an IEEE division is a ~10-instruction sequence per element, and at R elements per pixel it
-// made the region kernels VALU-bound
-__device__ __forceinline__ void sigmoid_bce(float x, float y, float& s, float& bce) {
-  const float e = __expf(-fabsf(x));
-  const float inv = __builtin_amdgcn_rcpf(1.f + e);
-  s = x >= 0.f ? inv : e * inv;
-  bce = fmaxf(x, 0.f) - x * y + __logf(1.f + e);
 }
 
 // COUNTS: region r is predicted where x > 0.  The reference thresholds sigmoid(x) > 0.5 (nnUNetTrainer.py:974); torch's fp32 sigmoid
@@ -444,12 +395,7 @@ __global__ __launch_bounds__(256) void dice_bce_partial_kernel(const float* __re
           cnt[R + r] += (m[j] && pred) ? 1 : 0;
           cnt[2 * R + r] += (m[j] && lab) ? 1 : 0;
         }
-        float s, bce;
-        sigmoid_bce(x[j], y, s, bce);
-        acc[0] += m[j] ? bce : 0.f;
-        acc[2 + 3 * r] += m[j] ? s * y : 0.f;
-        acc[2 + 3 * r + 1] += m[j] ? s : 0.f;
-        acc[2 + 3 * r + 2] += m[j] ? y : 0.f;
+        sigmoid_elem_fwd(x[j], y, m[j], r, acc);
       }
     }
   }
@@ -462,11 +408,7 @@ __global__ __launch_bounds__(256) void dice_bce_partial_kernel(const float* __re
 __global__ void dice_bce_coef_kernel(const float* __restrict__ sums, float* __restrict__ loss, float* __restrict__ coef, int R, int ign,
                                      float smooth, float grad_mult) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const float dc = dice_coefs(sums + 2, coef, R, smooth, grad_mult);
-  const float nv = sums[1];
-  const float bce_scale = nv > 0.f ? 1.f / (ign ? nv : nv * (float)R) : 0.f;
-  coef[2 * R] = bce_scale;
-  loss[0] = sums[0] * bce_scale - dc;
+  loss[0] = loss_finish(sums, sums + 2, coef, R, !ign, smooth, grad_mult, 1.f);
 }
 
 template <int R>
@@ -494,9 +436,7 @@ __global__ __launch_bounds__(256) void dice_bce_bwd_kernel(const float* __restri
       for (int j = 0; j < 4; j++) {
         const bool m = ((iw >> (8 * j)) & 0xffu) == 0u;
         const float y = ((yw >> (8 * j)) & 0xffu) ? 1.f : 0.f;
-        float s, bce;
-        sigmoid_bce(x[j], y, s, bce);
-        x[j] = m ? go * ((s - y) * bce_scale + (ca * y + cb) * s * (1.f - s)) : 0.f;
+        x[j] = m ? sigmoid_elem_bwd(x[j], y, ca, cb, bce_scale, go) : 0.f;
       }
       st4f(dp + (long)r * HW, vec, n, x);
     }
@@ -535,12 +475,43 @@ __global__ __launch_bounds__(256) void labels_to_regions_kernel(const int64_t* _
   }
 }
 
-}  // namespace
+bool counts_fit(int B, int64_t HW) { return (int64_t)B * HW < ((int64_t)1 << 31); }
 
-#define LOSS_R_SWITCH(R, CALL) \
-  switch (R) { case 1: { CALL(1); break; } case 2: { CALL(2); break; } case 3: { CALL(3); break; } case 4: { CALL(4); break; } \
-               case 5: { CALL(5); break; } case 6: { CALL(6); break; } case 7: { CALL(7); break; } case 8: { CALL(8); break; } \
-               default: return DU_ERR_UNSUPPORTED; }
+// The sums pass of a training loss (COUNTS = false) and of its validation twin (COUNTS = true: the same float code, plus the int32 count
+// rows behind the float rows of ws and counts_sum_kernel).  The entries check their arguments; these check the workspace and launch.
+template <bool COUNTS>
+int masked_sums_launch(const float* logits, const int64_t* target, float* sums, int64_t* counts, int64_t* accum, int B, int K, int64_t HW,
+                       int64_t ignore_label, float* ws, int64_t ws_elems, hipStream_t st) {
+  const int grid = masked_grid(quad_items(B, HW));
+  const int NS = 2 + 3 * (K - 1);
+  if (ws_elems < (int64_t)grid * (NS + (COUNTS ? 3 * K : 0))) return DU_ERR_BAD_ARG;
+  int* cws = COUNTS ? reinterpret_cast<int*>(ws + (long)grid * NS) : nullptr;
+  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16);
+#define CALL(KK) hipLaunchKernelGGL((dice_ce_masked_partial_kernel<KK, COUNTS>), dim3(grid), dim3(256), 0, st, logits, target, ws, cws, B, (long)HW, ignore_label, vec); \
+                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * (KK - 1)>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
+  LOSS_SWITCH(K, 2, CALL)
+#undef CALL
+  if (COUNTS) hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, K);
+  return du_check_launch();
+}
+
+template <bool COUNTS>
+int bce_sums_launch(const float* logits, const uint8_t* target, float* sums, int64_t* counts, int64_t* accum, int B, int R, int64_t HW,
+                    int has_ignore, float* ws, int64_t ws_elems, hipStream_t st) {
+  const int grid = masked_grid(quad_items(B, HW));
+  const int NS = 2 + 3 * R;
+  if (ws_elems < (int64_t)grid * (NS + (COUNTS ? 3 * R : 0))) return DU_ERR_BAD_ARG;
+  int* cws = COUNTS ? reinterpret_cast<int*>(ws + (long)grid * NS) : nullptr;
+  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 4);
+#define CALL(RR) hipLaunchKernelGGL((dice_bce_partial_kernel<RR, COUNTS>), dim3(grid), dim3(256), 0, st, logits, target, ws, cws, B, (long)HW, has_ignore, vec); \
+                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * RR>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
+  LOSS_SWITCH(R, 1, CALL)
+#undef CALL
+  if (COUNTS) hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, R);
+  return du_check_launch();
+}
+
+}  // namespace
 
 extern "C" int64_t du_dice_ce_masked_ws_elems(int B, int K, int64_t HW) {
   if (B <= 0 || K < 2 || K > 8 || HW <= 0) return 0;
@@ -552,15 +523,7 @@ extern "C" int du_dice_ce_masked_sums(const float* logits, const int64_t* target
   hipStream_t st = (hipStream_t)stream;
   if (!logits || !target || !sums || !ws || B <= 0 || HW <= 0) return DU_ERR_BAD_ARG;
   if (K < 2 || K > 8) return DU_ERR_UNSUPPORTED;
-  const int grid = masked_grid(quad_items(B, HW));
-  const int NS = 2 + 3 * (K - 1);
-  if (ws_elems < (int64_t)grid * NS) return DU_ERR_BAD_ARG;
-  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16);
-#define CALL(KK) hipLaunchKernelGGL((dice_ce_masked_partial_kernel<KK, false>), dim3(grid), dim3(256), 0, st, logits, target, ws, (int*)nullptr, B, (long)HW, ignore_label, vec); \
-                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * (KK - 1)>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
-  LOSS_K_SWITCH(K, CALL)
-#undef CALL
-  return du_check_launch();
+  return masked_sums_launch<false>(logits, target, sums, nullptr, nullptr, B, K, HW, ignore_label, ws, ws_elems, st);
 }
 
 extern "C" int du_dice_ce_masked_finish(const float* sums, float* loss, float* coef, int K, float smooth, float grad_mult, void* stream) {
@@ -579,7 +542,7 @@ extern "C" int du_dice_ce_masked_bwd(const float* logits, const int64_t* target,
   const int g = elem_grid(quad_items(B, HW));
   const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16) && al(dlogits, 16);
 #define CALL(KK) hipLaunchKernelGGL(dice_ce_masked_bwd_kernel<KK>, dim3(g), dim3(256), 0, st, logits, target, coef, grad_out, dlogits, B, (long)HW, ignore_label, vec)
-  LOSS_K_SWITCH(K, CALL)
+  LOSS_SWITCH(K, 2, CALL)
 #undef CALL
   return du_check_launch();
 }
@@ -594,15 +557,7 @@ extern "C" int du_dice_bce_sums(const float* logits, const uint8_t* target, floa
   hipStream_t st = (hipStream_t)stream;
   if (!logits || !target || !sums || !ws || B <= 0 || HW <= 0 || (has_ignore != 0 && has_ignore != 1)) return DU_ERR_BAD_ARG;
   if (R < 1 || R > MAXR) return DU_ERR_UNSUPPORTED;
-  const int grid = masked_grid(quad_items(B, HW));
-  const int NS = 2 + 3 * R;
-  if (ws_elems < (int64_t)grid * NS) return DU_ERR_BAD_ARG;
-  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 4);
-#define CALL(RR) hipLaunchKernelGGL((dice_bce_partial_kernel<RR, false>), dim3(grid), dim3(256), 0, st, logits, target, ws, (int*)nullptr, B, (long)HW, has_ignore, vec); \
-                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * RR>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
-  LOSS_R_SWITCH(R, CALL)
-#undef CALL
-  return du_check_launch();
+  return bce_sums_launch<false>(logits, target, sums, nullptr, nullptr, B, R, HW, has_ignore, ws, ws_elems, st);
 }
 
 extern "C" int du_dice_bce_finish(const float* sums, float* loss, float* coef, int R, int has_ignore, float smooth, float grad_mult,
@@ -622,7 +577,7 @@ extern "C" int du_dice_bce_bwd(const float* logits, const uint8_t* target, const
   const int g = elem_grid(quad_items(B, HW));
   const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 4) && al(dlogits, 16);
 #define CALL(RR) hipLaunchKernelGGL(dice_bce_bwd_kernel<RR>, dim3(g), dim3(256), 0, st, logits, target, coef, grad_out, dlogits, B, (long)HW, has_ignore, vec)
-  LOSS_R_SWITCH(R, CALL)
+  LOSS_SWITCH(R, 1, CALL)
 #undef CALL
   return du_check_launch();
 }
@@ -644,10 +599,6 @@ extern "C" int du_labels_to_regions(const int64_t* seg, const int64_t* table, ui
 // hard prediction, from ONE read of the logits.  counts (3, C) int64 = this step's [tp | fp | fn] over all C = K classes / R regions
 // (the host drops the background, :999-1006); accum (3, C) int64 += counts (NULL: none).  ws: the float partial rows, then the int32 count
 // rows (4-byte elements both).  int32 block partials: B * HW < 2^31.
-namespace {
-bool counts_fit(int B, int64_t HW) { return (int64_t)B * HW < ((int64_t)1 << 31); }
-}  // namespace
-
 extern "C" int64_t du_val_dice_ce_ws_elems(int B, int K, int64_t HW) {
   if (B <= 0 || K < 2 || K > 8 || HW <= 0) return 0;
   return (int64_t)loss_grid((long)B * HW) * (1 + 3 * (K - 1) + 3 * K);
@@ -663,7 +614,7 @@ extern "C" int du_val_dice_ce(const float* logits, const int64_t* target, float*
   if (ws_elems < (int64_t)grid * (NS + 3 * K)) return DU_ERR_BAD_ARG;
   int* cws = reinterpret_cast<int*>(ws + (long)grid * NS);
 #define CALL(KK) hipLaunchKernelGGL((dice_ce_partial_kernel<KK, true>), dim3(grid), dim3(256), 0, st, logits, target, ws, cws, B, (long)HW)
-  LOSS_K_SWITCH(K, CALL)
+  LOSS_SWITCH(K, 2, CALL)
 #undef CALL
   hipLaunchKernelGGL(dice_ce_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid, NS);
   hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, K);
@@ -680,17 +631,7 @@ extern "C" int du_val_dice_ce_masked(const float* logits, const int64_t* target,
   hipStream_t st = (hipStream_t)stream;
   if (!logits || !target || !sums || !counts || !ws || B <= 0 || HW <= 0) return DU_ERR_BAD_ARG;
   if (K < 2 || K > 8 || !counts_fit(B, HW)) return DU_ERR_UNSUPPORTED;
-  const int grid = masked_grid(quad_items(B, HW));
-  const int NS = 2 + 3 * (K - 1);
-  if (ws_elems < (int64_t)grid * (NS + 3 * K)) return DU_ERR_BAD_ARG;
-  int* cws = reinterpret_cast<int*>(ws + (long)grid * NS);
-  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16);
-#define CALL(KK) hipLaunchKernelGGL((dice_ce_masked_partial_kernel<KK, true>), dim3(grid), dim3(256), 0, st, logits, target, ws, cws, B, (long)HW, ignore_label, vec); \
-                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * (KK - 1)>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
-  LOSS_K_SWITCH(K, CALL)
-#undef CALL
-  hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, K);
-  return du_check_launch();
+  return masked_sums_launch<true>(logits, target, sums, counts, accum, B, K, HW, ignore_label, ws, ws_elems, st);
 }
 
 extern "C" int64_t du_val_dice_bce_ws_elems(int B, int R, int64_t HW) {
@@ -703,17 +644,7 @@ extern "C" int du_val_dice_bce(const float* logits, const uint8_t* target, float
   hipStream_t st = (hipStream_t)stream;
   if (!logits || !target || !sums || !counts || !ws || B <= 0 || HW <= 0 || (has_ignore != 0 && has_ignore != 1)) return DU_ERR_BAD_ARG;
   if (R < 1 || R > MAXR || !counts_fit(B, HW)) return DU_ERR_UNSUPPORTED;
-  const int grid = masked_grid(quad_items(B, HW));
-  const int NS = 2 + 3 * R;
-  if (ws_elems < (int64_t)grid * (NS + 3 * R)) return DU_ERR_BAD_ARG;
-  int* cws = reinterpret_cast<int*>(ws + (long)grid * NS);
-  const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 4);
-#define CALL(RR) hipLaunchKernelGGL((dice_bce_partial_kernel<RR, true>), dim3(grid), dim3(256), 0, st, logits, target, ws, cws, B, (long)HW, has_ignore, vec); \
-                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * RR>, dim3(1), dim3(256), 0, st, (const float*)ws, sums, grid)
-  LOSS_R_SWITCH(R, CALL)
-#undef CALL
-  hipLaunchKernelGGL(counts_sum_kernel, dim3(1), dim3(256), 0, st, (const int*)cws, counts, accum, grid, R);
-  return du_check_launch();
+  return bce_sums_launch<true>(logits, target, sums, counts, accum, B, R, HW, has_ignore, ws, ws_elems, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -827,12 +758,7 @@ __global__ __launch_bounds__(256) void ds_partial_kernel(DsTable d, const int64_
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           const float y = (t[j] >= 0 && t[j] < 64 && ((tb[r] >> t[j]) & 1ull)) ? 1.f : 0.f;
-          float s, bce;
-          sigmoid_bce(x[j], y, s, bce);
-          acc[0] += m[j] ? bce : 0.f;
-          acc[2 + 3 * r] += m[j] ? s * y : 0.f;
-          acc[2 + 3 * r + 1] += m[j] ? s : 0.f;
-          acc[2 + 3 * r + 2] += m[j] ? y : 0.f;
+          sigmoid_elem_fwd(x[j], y, m[j], r, acc);
         }
       }
     } else {
@@ -842,23 +768,10 @@ __global__ __launch_bounds__(256) void ds_partial_kernel(DsTable d, const int64_
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const bool valid = j < n && t[j] != ignore;
-        float mx = -INFINITY;
+        float x[N];
 #pragma unroll
-        for (int k = 0; k < N; k++) mx = fmaxf(mx, v[k][j]);
-        float e[N], se = 0.f, xt = mx;
-#pragma unroll
-        for (int k = 0; k < N; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
-        const float inv = 1.f / se;
-        acc[0] += valid ? softmax_nll(mx, xt, se) : 0.f;
-        acc[1] += valid ? 1.f : 0.f;
-#pragma unroll
-        for (int k = 1; k < N; k++) {
-          const float pk = e[k] * inv;
-          const bool hit = valid && k == t[j];
-          acc[2 + 3 * (k - 1)] += hit ? pk : 0.f;
-          acc[2 + 3 * (k - 1) + 1] += valid ? pk : 0.f;
-          acc[2 + 3 * (k - 1) + 2] += hit ? 1.f : 0.f;
-        }
+        for (int k = 0; k < N; k++) x[k] = v[k][j];
+        softmax_pixel_fwd<N>(x, t[j], valid, acc, [&](float nll) { return valid ? nll : 0.f; });
       }
     }
   }
@@ -875,26 +788,8 @@ __global__ __launch_bounds__(256) void ds_rows_sum_kernel(DsTable d, const float
 #pragma unroll
   for (int i = 1; i < DS_MAX; i++) if (s == i) { first = d.s[i].first; nblk = d.s[i].nblk; }
   float acc[NS];
-#pragma unroll
-  for (int i = 0; i < NS; i++) acc[i] = 0.f;
-  for (int b = threadIdx.x; b < nblk; b += 256) {
-    const float* row = part + (long)(first + b) * NS;
-#pragma unroll
-    for (int i = 0; i < NS; i++) acc[i] += row[i];
-  }
-  __shared__ float red[4][NS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NS; i++) {
-    const float v = wave_sum(acc[i]);
-    if (lane == 0) red[wave][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    const int i = threadIdx.x;
-    const float v = red[0][i] + red[1][i] + red[2][i] + red[3][i];
-    sums[i < 2 ? 2 * s + i : 2 * d.S + 3 * CD * s + (i - 2)] = v;
-  }
+  thread_rows_sum<NS>(part + (long)first * NS, nblk, acc);
+  block_columns_store<NS>(acc, [&](int i) { return sums + (i < 2 ? 2 * s + i : 2 * d.S + 3 * CD * s + (i - 2)); });
 }
 
 // loss = [total, loss_0 .. loss_{S-1}] (0 for an inactive scale); coef (S, 2 CD + 1) = per scale [(ca_c, cb_c) c < CD, CE / BCE scale],
@@ -908,11 +803,7 @@ __global__ void ds_finish_kernel(DsTable d, const float* __restrict__ sums, floa
     float* cf = coef + s * (2 * CD + 1);
     float l = 0.f;
     if (w != 0.f) {
-      const float dc = dice_coefs(sums + 2 * d.S + 3 * CD * s, cf, CD, smooth, grad_mult * w);
-      const float nv = sums[2 * s + 1];
-      const float scale = nv > 0.f ? 1.f / ((sig && !ign) ? nv * (float)CD : nv) : 0.f;
-      cf[2 * CD] = scale * w;
-      l = sums[2 * s] * scale - dc;
+      l = loss_finish(sums + 2 * s, sums + 2 * d.S + 3 * CD * s, cf, CD, sig && !ign, smooth, grad_mult, w);
     } else {
       for (int i = 0; i < 2 * CD + 1; i++) cf[i] = 0.f;
     }
@@ -938,12 +829,7 @@ __global__ __launch_bounds__(256) void ds_bwd_kernel(DsTable d, const int64_t* _
   const DsScale sc = ds_scale_of_block(d, si);
   const float* cf = coef + si * (2 * CD + 1);
   float ca[N], cb[N];
-#pragma unroll
-  for (int c = 0; c < N; c++) {
-    const int q = SIG ? c : c - 1;
-    ca[c] = q >= 0 ? cf[2 * q] : 0.f;
-    cb[c] = q >= 0 ? cf[2 * q + 1] : 0.f;
-  }
+  load_dice_coefs<N, CD>(cf, ca, cb);
   const float scale = cf[2 * CD];
   const float go = gout ? gout[0] : 1.f;
   const long HW = (long)sc.h * sc.w, HWf = (long)d.H * d.W;
@@ -970,9 +856,7 @@ __global__ __launch_bounds__(256) void ds_bwd_kernel(DsTable d, const int64_t* _
         for (int j = 0; j < 4; j++) {
           const bool m = t[j] != ignore;
           const float y = (t[j] >= 0 && t[j] < 64 && ((tb[r] >> t[j]) & 1ull)) ? 1.f : 0.f;
-          float s, bce;
-          sigmoid_bce(x[j], y, s, bce);
-          x[j] = m ? go * ((s - y) * scale + (ca[r] * y + cb[r]) * s * (1.f - s)) : 0.f;
+          x[j] = m ? sigmoid_elem_bwd(x[j], y, ca[r], cb[r], scale, go) : 0.f;
         }
         st4f(dp + (long)r * HW, vec, n, x);
       }
@@ -983,6 +867,7 @@ __global__ __launch_bounds__(256) void ds_bwd_kernel(DsTable d, const int64_t* _
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const bool valid = t[j] != ignore;
+        const float ce_scale_j = scale;
         float mx = -INFINITY;
 #pragma unroll
         for (int k = 0; k < N; k++) mx = fmaxf(mx, v[k][j]);
@@ -999,7 +884,7 @@ __global__ __launch_bounds__(256) void ds_bwd_kernel(DsTable d, const int64_t* _
         }
 #pragma unroll
         for (int k = 0; k < N; k++)
-          v[k][j] = valid ? go * ((v[k][j] - (k == t[j] ? 1.f : 0.f)) * scale + v[k][j] * (g[k] - dot)) : 0.f;
+          v[k][j] = valid ? go * ((v[k][j] - (k == t[j] ? 1.f : 0.f)) * ce_scale_j + v[k][j] * (g[k] - dot)) : 0.f;
       }
 #pragma unroll
       for (int k = 0; k < N; k++) st4f(dp + (long)k * HW, vec, n, v[k]);
@@ -1101,12 +986,12 @@ extern "C" int du_ds_loss_sums(int mode, const float* const* logits, const int64
   if (mode == 0) {
 #define CALL(KK) hipLaunchKernelGGL((ds_partial_kernel<false, KK>), dim3(total), dim3(256), 0, st, d, target, table, ws, ignore); \
                  hipLaunchKernelGGL(ds_rows_sum_kernel<KK - 1>, dim3(S), dim3(256), 0, st, d, (const float*)ws, sums)
-    LOSS_K_SWITCH(C, CALL)
+    LOSS_SWITCH(C, 2, CALL)
 #undef CALL
   } else {
 #define CALL(RR) hipLaunchKernelGGL((ds_partial_kernel<true, RR>), dim3(total), dim3(256), 0, st, d, target, table, ws, ignore); \
                  hipLaunchKernelGGL(ds_rows_sum_kernel<RR>, dim3(S), dim3(256), 0, st, d, (const float*)ws, sums)
-    LOSS_R_SWITCH(C, CALL)
+    LOSS_SWITCH(C, 1, CALL)
 #undef CALL
   }
   return du_check_launch();
@@ -1144,11 +1029,11 @@ extern "C" int du_ds_loss_bwd(int mode, const float* const* logits, const int64_
   const int64_t ignore = has_ignore ? ignore_label : DS_NO_IGNORE;
   if (mode == 0) {
 #define CALL(KK) hipLaunchKernelGGL((ds_bwd_kernel<false, KK>), dim3(total), dim3(256), 0, st, d, target, table, coef, grad_out, ignore)
-    LOSS_K_SWITCH(C, CALL)
+    LOSS_SWITCH(C, 2, CALL)
 #undef CALL
   } else {
 #define CALL(RR) hipLaunchKernelGGL((ds_bwd_kernel<true, RR>), dim3(total), dim3(256), 0, st, d, target, table, coef, grad_out, ignore)
-    LOSS_R_SWITCH(C, CALL)
+    LOSS_SWITCH(C, 1, CALL)
 #undef CALL
   }
   return du_check_launch();

@@ -41,20 +41,6 @@ __device__ __forceinline__ void ld4k(const uint32_t* __restrict__ keys, long i, 
   }
 }
 
-// ONE block adds the per-block partial rows (blocks x NS), fixed order (the second stage of the masked losses)
-template <int NS>
-__global__ __launch_bounds__(256) void topk_rows_sum_kernel(const float* __restrict__ part, float* __restrict__ sums, int blocks) {
-  float acc[NS];
-#pragma unroll
-  for (int i = 0; i < NS; i++) acc[i] = 0.f;
-  for (int b = threadIdx.x; b < blocks; b += 256) {
-    const float* row = part + (long)b * NS;
-#pragma unroll
-    for (int i = 0; i < NS; i++) acc[i] += row[i];
-  }
-  block_partial_store<NS>(acc, sums);
-}
-
 __global__ __launch_bounds__(256) void topk_init_kernel(uint32_t* __restrict__ hist_state, int words) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < words; i += gridDim.x * 256) hist_state[i] = 0u;
 }
@@ -84,26 +70,12 @@ __global__ __launch_bounds__(256) void topk_values_kernel(const float* __restric
     float ce[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
+      float x[K];
+#pragma unroll
+      for (int k = 0; k < K; k++) x[k] = v[k][j];
       const bool valid = t[j] != ignore;
-      float mx = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < K; k++) mx = fmaxf(mx, v[k][j]);
-      float e[K], se = 0.f, xt = mx;
-#pragma unroll
-      for (int k = 0; k < K; k++) { e[k] = __expf(v[k][j] - mx); se += e[k]; if (k == t[j]) xt = v[k][j]; }
-      const float inv = 1.f / se;
-      const float nll = softmax_nll(mx, xt, se);
-      ce[j] = (valid && nll > 0.f) ? nll : 0.f;            // +0 for an ignored voxel, for -0 and for a nan: the bits order as integers
-      acc[0] += ce[j];
-      acc[1] += valid ? 1.f : 0.f;
-#pragma unroll
-      for (int k = 1; k < K; k++) {
-        const float pk = e[k] * inv;
-        const bool hit = valid && k == t[j];
-        acc[2 + 3 * (k - 1)] += hit ? pk : 0.f;
-        acc[2 + 3 * (k - 1) + 1] += valid ? pk : 0.f;
-        acc[2 + 3 * (k - 1) + 2] += hit ? 1.f : 0.f;
-      }
+      // +0 for an ignored voxel, for -0 and for a nan: the bits order as integers
+      ce[j] = softmax_pixel_fwd<K>(x, t[j], valid, acc, [&](float nll) { return (nll > 0.f && valid) ? nll : 0.f; });
     }
     st4f(values + b * HW + r0, vec, n, ce);
 #pragma unroll
@@ -359,9 +331,7 @@ __global__ __launch_bounds__(256) void topk_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ gout, float* __restrict__ dlogits, int B, long HW,
                                                        int64_t ignore, bool vec) {
   float ca[K], cb[K];
-  ca[0] = 0.f; cb[0] = 0.f;
-#pragma unroll
-  for (int c = 1; c < K; c++) { ca[c] = coef[2 * (c - 1)]; cb[c] = coef[2 * (c - 1) + 1]; }
+  load_dice_coefs<K, K - 1>(coef, ca, cb);
   const float inv_k = coef[2 * (K - 1)];
   const float go = gout ? gout[0] : 1.f;
   const long nq = (HW + 3) >> 2, items = (long)B * nq;
@@ -378,7 +348,7 @@ __global__ __launch_bounds__(256) void topk_bwd_kernel(const float* __restrict__
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const bool valid = t[j] != ignore;
-      const float ce_scale = ((sw >> (8 * j)) & 0xffu) ? inv_k : 0.f;
+      const float ce_scale_j = ((sw >> (8 * j)) & 0xffu) ? inv_k : 0.f;
       float mx = -INFINITY;
 #pragma unroll
       for (int k = 0; k < K; k++) mx = fmaxf(mx, v[k][j]);
@@ -395,7 +365,7 @@ __global__ __launch_bounds__(256) void topk_bwd_kernel(const float* __restrict__
       }
 #pragma unroll
       for (int k = 0; k < K; k++)
-        v[k][j] = valid ? go * ((v[k][j] - (k == t[j] ? 1.f : 0.f)) * ce_scale + v[k][j] * (g[k] - dot)) : 0.f;
+        v[k][j] = valid ? go * ((v[k][j] - (k == t[j] ? 1.f : 0.f)) * ce_scale_j + v[k][j] * (g[k] - dot)) : 0.f;
     }
     float* dp = dlogits + b * K * HW + r0;
 #pragma unroll
@@ -436,10 +406,6 @@ bool shape_ok(int B, int64_t HW) { return B > 0 && HW > 0 && (int64_t)B * HW < (
 
 }  // namespace
 
-#define TOPK_K_SWITCH(K, CALL) \
-  switch (K) { case 2: { CALL(2); break; } case 3: { CALL(3); break; } case 4: { CALL(4); break; } case 5: { CALL(5); break; } \
-               case 6: { CALL(6); break; } case 7: { CALL(7); break; } case 8: { CALL(8); break; } default: return DU_ERR_UNSUPPORTED; }
-
 extern "C" int64_t du_topk_loss_ws_elems(int B, int K, int64_t HW) {
   if (K < 2 || K > 8 || !shape_ok(B, HW)) return 0;
   return layout_of(B, K, HW).total;
@@ -465,8 +431,8 @@ extern "C" int du_topk_loss_fwd(const float* logits, const int64_t* target, floa
   const uint32_t* keys = (const uint32_t*)values;
   hipLaunchKernelGGL(topk_init_kernel, dim3(4), dim3(256), 0, st, hist, HIST_WORDS + STATE_WORDS);
 #define CALL(KK) hipLaunchKernelGGL(topk_values_kernel<KK>, dim3(grid), dim3(256), 0, st, logits, target, values, part, hist, B, (long)HW, ignore, vec); \
-                 hipLaunchKernelGGL(topk_rows_sum_kernel<2 + 3 * (KK - 1)>, dim3(1), dim3(256), 0, st, (const float*)part, sums, grid)
-  TOPK_K_SWITCH(K, CALL)
+                 hipLaunchKernelGGL(partial_rows_sum_kernel<2 + 3 * (KK - 1)>, dim3(1), dim3(256), 0, st, (const float*)part, sums, grid)
+  LOSS_SWITCH(K, 2, CALL)
 #undef CALL
   hipLaunchKernelGGL(topk_sweep_kernel<2>, dim3(s.G), dim3(256), 0, st, keys, (long)N, s.CW, hist, state, (uint32_t)k_vox, kvec);
   hipLaunchKernelGGL(topk_sweep_kernel<3>, dim3(s.G), dim3(256), 0, st, keys, (long)N, s.CW, hist, state, (uint32_t)k_vox, kvec);
@@ -503,7 +469,7 @@ extern "C" int du_topk_loss_bwd(const float* logits, const int64_t* target, cons
   const int g = elem_grid(quad_items(B, HW));
   const bool vec = HW % 4 == 0 && al(logits, 16) && al(target, 16) && al(dlogits, 16) && al(sel, 4);
 #define CALL(KK) hipLaunchKernelGGL(topk_bwd_kernel<KK>, dim3(g), dim3(256), 0, st, logits, target, sel, coef, grad_out, dlogits, B, (long)HW, ignore, vec)
-  TOPK_K_SWITCH(K, CALL)
+  LOSS_SWITCH(K, 2, CALL)
 #undef CALL
   return du_check_launch();
 }

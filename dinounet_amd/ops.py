@@ -2362,6 +2362,51 @@ def squeeze_excite(x, w1, b1, w2, b2, shortcut=None):
     return _SqueezeExcite.apply(x, w1, b1, w2, b2, shortcut)
 
 
+def _labels2d(t, B, HW):
+    """integer labels (B,1,H,W) as the (B, HW) int64 contiguous map the label kernels read"""
+    t = t.reshape(B, HW)
+    if t.dtype != torch.int64:
+        t = t.long()
+    return t.contiguous()
+
+
+def _dice_group(sums, group, off):
+    """all-reduce the Dice slice sums[off:] of a fused loss (CE / BCE and n_valid stay local; AllGatherGrad + sum,
+    utilities/ddp_allgather.py:25-48) -> grad_mult.  off: 1 plain labels, 2 masked / regions / top-k, 2 S deep supervision."""
+    if group is not None and torch.distributed.is_initialized():   # (the losses of training.py pass a group only for a DDP loss)
+        _small_all_reduce(sums[off:], group, "dice_sums")
+        return float(torch.distributed.get_world_size(group))
+    return 1.0
+
+
+def _loss_forward(dev, n, n_sums, n_loss, n_coef, dice_off, group, sums_call, finish_call, ws_dtype=torch.float32):
+    """The forward sequence of every fused loss: the workspace of n elements and the sums, sums_call(ws, sums), the all-reduce of
+    sums[dice_off:] over `group`, loss and coef, finish_call(sums, loss, coef, grad_mult, ws) -> (loss, coef)."""
+    ws = torch.empty(n, dtype=ws_dtype, device=dev)
+    sums = torch.empty(n_sums, dtype=torch.float32, device=dev)
+    sums_call(ws, sums)
+    mult = _dice_group(sums, group, dice_off)
+    loss = torch.empty(n_loss, dtype=torch.float32, device=dev)
+    coef = torch.empty(n_coef, dtype=torch.float32, device=dev)
+    finish_call(sums, loss, coef, mult, ws)
+    return loss, coef
+
+
+def _finish_dice_ce(K, npix, smooth):
+    return lambda sums, loss, coef, mult, ws: _lib.check(
+        _lib.lib().du_dice_ce_finish(_p(sums), _p(loss), _p(coef), K, npix, float(smooth), mult, _st()), "du_dice_ce_finish")
+
+
+def _finish_dice_ce_masked(K, smooth):
+    return lambda sums, loss, coef, mult, ws: _lib.check(
+        _lib.lib().du_dice_ce_masked_finish(_p(sums), _p(loss), _p(coef), K, float(smooth), mult, _st()), "du_dice_ce_masked_finish")
+
+
+def _finish_dice_bce(R, u, smooth):
+    return lambda sums, loss, coef, mult, ws: _lib.check(
+        _lib.lib().du_dice_bce_finish(_p(sums), _p(loss), _p(coef), R, u, float(smooth), mult, _st()), "du_dice_bce_finish")
+
+
 class _DiceCE(torch.autograd.Function):
     """DC_and_CE_loss of the reference trainer (compound_losses.py:8-56; MemoryEfficientSoftDiceLoss batch_dice, do_bg=False,
     smooth, dice.py:58-119) on fp32 NCHW logits, fused: one pass for the softmax sums, one pass for d loss / d logits.
@@ -2372,24 +2417,15 @@ class _DiceCE(torch.autograd.Function):
         logits = logits.float().contiguous()
         B, K, H, W = logits.shape
         HW = H * W
-        tgt = target.reshape(B, HW)
-        if tgt.dtype != torch.int64:
-            tgt = tgt.long()
-        tgt = tgt.contiguous()
+        tgt = _labels2d(target, B, HW)
         L = _lib.lib()
         n = int(L.du_dice_ce_ws_elems(B, K, HW))
         if n <= 0:
             raise RuntimeError(f"dinounet_hip: fused Dice+CE supports 2..8 classes, got {K}")
-        ws = torch.empty(n, dtype=torch.float32, device=logits.device)
-        sums = torch.empty(1 + 3 * (K - 1), dtype=torch.float32, device=logits.device)
-        _lib.check(L.du_dice_ce_sums(_p(logits), _p(tgt), _p(sums), B, K, HW, _p(ws), n, _st()), "du_dice_ce_sums")
-        mult = 1.0
-        if group is not None and torch.distributed.is_initialized():   # (dc_and_ce_loss passes a group only for a DDP loss)
-            _small_all_reduce(sums[1:], group, "dice_sums")
-            mult = float(torch.distributed.get_world_size(group))
-        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-        coef = torch.empty(2 * (K - 1), dtype=torch.float32, device=logits.device)
-        _lib.check(L.du_dice_ce_finish(_p(sums), _p(loss), _p(coef), K, B * HW, float(smooth), mult, _st()), "du_dice_ce_finish")
+        loss, coef = _loss_forward(
+            logits.device, n, 1 + 3 * (K - 1), 1, 2 * (K - 1), 1, group,
+            lambda ws, sums: _lib.check(L.du_dice_ce_sums(_p(logits), _p(tgt), _p(sums), B, K, HW, _p(ws), n, _st()), "du_dice_ce_sums"),
+            _finish_dice_ce(K, B * HW, smooth))
         ctx.save_for_backward(logits, tgt, coef)
         return loss.view(())
 
@@ -2409,14 +2445,6 @@ def dice_ce_loss(logits, target, smooth=1e-5, group=None):
     return _DiceCE.apply(logits, target, smooth, group)
 
 
-def _dice_group(sums, group, what):
-    """all-reduce the Dice slice sums[2:] of a masked / region loss (CE / BCE and n_valid stay local) -> grad_mult"""
-    if group is not None and torch.distributed.is_initialized():
-        _small_all_reduce(sums[2:], group, what)
-        return float(torch.distributed.get_world_size(group))
-    return 1.0
-
-
 class _DiceCEMasked(torch.autograd.Function):
     """DC_and_CE_loss(ignore_label) of the reference trainer (compound_losses.py:31-56; MemoryEfficientSoftDiceLoss with loss_mask,
     dice.py:72-119) on fp32 NCHW logits, fused like _DiceCE.  CE is the mean over valid pixels and exactly 0 when none is valid, decided on
@@ -2427,22 +2455,16 @@ class _DiceCEMasked(torch.autograd.Function):
         logits = logits.float().contiguous()
         B, K, H, W = logits.shape
         HW = H * W
-        tgt = target.reshape(B, HW)
-        if tgt.dtype != torch.int64:
-            tgt = tgt.long()
-        tgt = tgt.contiguous()
+        tgt = _labels2d(target, B, HW)
         L = _lib.lib()
         n = int(L.du_dice_ce_masked_ws_elems(B, K, HW))
         if n <= 0:
             raise RuntimeError(f"dinounet_hip: fused Dice+CE with an ignore label supports 2..8 classes, got {K}")
-        ws = torch.empty(n, dtype=torch.float32, device=logits.device)
-        sums = torch.empty(2 + 3 * (K - 1), dtype=torch.float32, device=logits.device)
-        _lib.check(L.du_dice_ce_masked_sums(_p(logits), _p(tgt), _p(sums), B, K, HW, int(ignore_label), _p(ws), n, _st()),
-                   "du_dice_ce_masked_sums")
-        mult = _dice_group(sums, group, "dice_sums")
-        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-        coef = torch.empty(2 * (K - 1) + 1, dtype=torch.float32, device=logits.device)
-        _lib.check(L.du_dice_ce_masked_finish(_p(sums), _p(loss), _p(coef), K, float(smooth), mult, _st()), "du_dice_ce_masked_finish")
+        loss, coef = _loss_forward(
+            logits.device, n, 2 + 3 * (K - 1), 1, 2 * (K - 1) + 1, 2, group,
+            lambda ws, sums: _lib.check(L.du_dice_ce_masked_sums(_p(logits), _p(tgt), _p(sums), B, K, HW, int(ignore_label), _p(ws), n,
+                                                                 _st()), "du_dice_ce_masked_sums"),
+            _finish_dice_ce_masked(K, smooth))
         ctx.save_for_backward(logits, tgt, coef)
         ctx.ignore_label = int(ignore_label)
         return loss.view(())
@@ -2476,10 +2498,7 @@ class _TopKLoss(torch.autograd.Function):
         logits = logits.float().contiguous()
         B, K, H, W = logits.shape
         HW = H * W
-        tgt = target.reshape(B, HW)
-        if tgt.dtype != torch.int64:
-            tgt = tgt.long()
-        tgt = tgt.contiguous()
+        tgt = _labels2d(target, B, HW)
         L = _lib.lib()
         n = int(L.du_topk_loss_ws_elems(B, K, HW))
         if n <= 0:
@@ -2487,18 +2506,17 @@ class _TopKLoss(torch.autograd.Function):
                                f"{B * HW} voxels")
         dev = logits.device
         has_ign, ign = (0, 0) if ignore_label is None else (1, int(ignore_label))
-        ws = torch.empty(n, dtype=torch.int32, device=dev)
         values = torch.empty((B, HW), dtype=torch.float32, device=dev)
-        sums = torch.empty(2 + 3 * (K - 1), dtype=torch.float32, device=dev)
-        _lib.check(L.du_topk_loss_fwd(_p(logits), _p(tgt), _p(values), _p(sums), B, K, HW, has_ign, ign, int(k_vox), _p(ws), n, _st()),
-                   "du_topk_loss_fwd")
-        mult = _dice_group(sums, group, "dice_sums") if dice else 1.0
         sel = torch.empty((B, HW), dtype=torch.uint8, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        coef = torch.empty(2 * (K - 1) + 1, dtype=torch.float32, device=dev)
         info = torch.empty(4, dtype=torch.int32, device=dev)
-        _lib.check(L.du_topk_loss_finish(_p(sums), _p(values), _p(ws), n, _p(sel), _p(loss), _p(coef), _p(info), B, K, HW, int(k_vox),
-                                         1 if dice else 0, float(smooth), mult, _st()), "du_topk_loss_finish")
+        loss, coef = _loss_forward(
+            dev, n, 2 + 3 * (K - 1), 1, 2 * (K - 1) + 1, 2, group if dice else None,
+            lambda ws, sums: _lib.check(L.du_topk_loss_fwd(_p(logits), _p(tgt), _p(values), _p(sums), B, K, HW, has_ign, ign, int(k_vox),
+                                                           _p(ws), n, _st()), "du_topk_loss_fwd"),
+            lambda sums, loss, coef, mult, ws: _lib.check(
+                L.du_topk_loss_finish(_p(sums), _p(values), _p(ws), n, _p(sel), _p(loss), _p(coef), _p(info), B, K, HW, int(k_vox),
+                                      1 if dice else 0, float(smooth), mult, _st()), "du_topk_loss_finish"),
+            ws_dtype=torch.int32)
         ctx.save_for_backward(logits, tgt, sel, coef)
         ctx.ignore = (has_ign, ign)
         thr = info[:1].view(torch.float32).view(())
@@ -2554,13 +2572,10 @@ class _DiceBCE(torch.autograd.Function):
         n = int(L.du_dice_bce_ws_elems(B, R, HW))
         if n <= 0:
             raise RuntimeError(f"dinounet_hip: fused Dice+BCE supports 1..8 regions, got {R}")
-        ws = torch.empty(n, dtype=torch.float32, device=logits.device)
-        sums = torch.empty(2 + 3 * R, dtype=torch.float32, device=logits.device)
-        _lib.check(L.du_dice_bce_sums(_p(logits), _p(tgt), _p(sums), B, R, HW, u, _p(ws), n, _st()), "du_dice_bce_sums")
-        mult = _dice_group(sums, group, "dice_sums")
-        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-        coef = torch.empty(2 * R + 1, dtype=torch.float32, device=logits.device)
-        _lib.check(L.du_dice_bce_finish(_p(sums), _p(loss), _p(coef), R, u, float(smooth), mult, _st()), "du_dice_bce_finish")
+        loss, coef = _loss_forward(
+            logits.device, n, 2 + 3 * R, 1, 2 * R + 1, 2, group,
+            lambda ws, sums: _lib.check(L.du_dice_bce_sums(_p(logits), _p(tgt), _p(sums), B, R, HW, u, _p(ws), n, _st()), "du_dice_bce_sums"),
+            _finish_dice_bce(R, u, smooth))
         ctx.save_for_backward(logits, tgt, coef)
         ctx.u = u
         return loss.view(())
@@ -2586,10 +2601,7 @@ def labels_to_regions(seg, table, ignore_label=None):
     u = 1 with an ignore label (last plane = [seg == ignore_label])."""
     _req(seg, table)
     B, H, W = seg.shape[0], seg.shape[-2], seg.shape[-1]
-    s = seg.reshape(B, H * W)
-    if s.dtype != torch.int64:
-        s = s.long()
-    s = s.contiguous()
+    s = _labels2d(seg, B, H * W)
     R = table.numel()
     u = 0 if ignore_label is None else 1
     out = torch.empty((B, R + u, H, W), dtype=torch.uint8, device=seg.device)
@@ -2609,10 +2621,7 @@ class _DSSegLoss(torch.autograd.Function):
         S = len(outs)
         B, Cn = outs[0].shape[0], outs[0].shape[1]
         H, W = target.shape[-2], target.shape[-1]
-        tgt = target.reshape(B, H * W)
-        if tgt.dtype != torch.int64:
-            tgt = tgt.long()
-        tgt = tgt.contiguous()
+        tgt = _labels2d(target, B, H * W)
         dev = tgt.device
         xs = [o.float().contiguous() if w != 0.0 else None for o, w in zip(outs, weights)]
         hs = (C.c_int * S)(*[int(o.shape[2]) for o in outs])
@@ -2629,17 +2638,12 @@ class _DSSegLoss(torch.autograd.Function):
             raise RuntimeError(f"dinounet_hip: the fused deep-supervision loss supports 1..4 scales no larger than the target, 2..8 classes "
                                f"or 1..8 regions and at least one non-zero weight; got {S} scales {[tuple(o.shape) for o in outs]}, "
                                f"target {(H, W)}, weights {list(weights)}")
-        ws = torch.empty(n, dtype=torch.float32, device=dev)
-        sums = torch.empty(S * (2 + 3 * CD), dtype=torch.float32, device=dev)
-        _lib.check(L.du_ds_loss_sums(m, ptrs, _p(tgt), _p(table), _p(sums), B, Cn, H, W, S, hs, wd, wt, u, ig, _p(ws), n, _st()),
-                   "du_ds_loss_sums")
-        mult = 1.0
-        if group is not None and torch.distributed.is_initialized():
-            _small_all_reduce(sums[2 * S:], group, "dice_sums")           # the Dice slices of every scale in one collective
-            mult = float(torch.distributed.get_world_size(group))
-        loss = torch.empty(1 + S, dtype=torch.float32, device=dev)
-        coef = torch.empty(S * (2 * CD + 1), dtype=torch.float32, device=dev)
-        _lib.check(L.du_ds_loss_finish(m, _p(sums), _p(loss), _p(coef), Cn, S, wt, u, float(smooth), mult, _st()), "du_ds_loss_finish")
+        loss, coef = _loss_forward(                     # sums[2 S:]: the Dice slices of every scale in one collective
+            dev, n, S * (2 + 3 * CD), 1 + S, S * (2 * CD + 1), 2 * S, group,
+            lambda ws, sums: _lib.check(L.du_ds_loss_sums(m, ptrs, _p(tgt), _p(table), _p(sums), B, Cn, H, W, S, hs, wd, wt, u, ig, _p(ws), n,
+                                                          _st()), "du_ds_loss_sums"),
+            lambda sums, loss, coef, mult, ws: _lib.check(
+                L.du_ds_loss_finish(m, _p(sums), _p(loss), _p(coef), Cn, S, wt, u, float(smooth), mult, _st()), "du_ds_loss_finish"))
         ctx.save_for_backward(tgt, coef, table, *[x for x in xs if x is not None])
         ctx.cfg = (m, u, ig, S, B, Cn, H, W, [float(w) for w in weights], [tuple(o.shape) for o in outs], table is not None)
         losses = loss[1:]
@@ -2724,34 +2728,25 @@ def val_dice_ce(logits, target, ignore_label=None, smooth=1e-5, group=None, coun
     logits = logits.float().contiguous()
     B, K, H, W = logits.shape
     HW = H * W
-    tgt = target.reshape(B, HW)
-    if tgt.dtype != torch.int64:
-        tgt = tgt.long()
-    tgt = tgt.contiguous()
+    tgt = _labels2d(target, B, HW)
     L = _lib.lib()
     masked = ignore_label is not None
     n = int((L.du_val_dice_ce_masked_ws_elems if masked else L.du_val_dice_ce_ws_elems)(B, K, HW))
     if n <= 0:
         raise RuntimeError(f"dinounet_hip: the fused validation pass supports 2..8 classes, got {K}")
     counts = _val_bufs(K, counts, accum, logits.device)
-    ws = torch.empty(n, dtype=torch.float32, device=logits.device)
-    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     if masked:
-        sums = torch.empty(2 + 3 * (K - 1), dtype=torch.float32, device=logits.device)
-        coef = torch.empty(2 * (K - 1) + 1, dtype=torch.float32, device=logits.device)
-        _lib.check(L.du_val_dice_ce_masked(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, K, HW, int(ignore_label), _p(ws), n,
-                                           _st()), "du_val_dice_ce_masked")
-        mult = _dice_group(sums, group, "dice_sums")
-        _lib.check(L.du_dice_ce_masked_finish(_p(sums), _p(loss), _p(coef), K, float(smooth), mult, _st()), "du_dice_ce_masked_finish")
+        loss, _ = _loss_forward(
+            logits.device, n, 2 + 3 * (K - 1), 1, 2 * (K - 1) + 1, 2, group,
+            lambda ws, sums: _lib.check(L.du_val_dice_ce_masked(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, K, HW,
+                                                                int(ignore_label), _p(ws), n, _st()), "du_val_dice_ce_masked"),
+            _finish_dice_ce_masked(K, smooth))
     else:
-        sums = torch.empty(1 + 3 * (K - 1), dtype=torch.float32, device=logits.device)
-        coef = torch.empty(2 * (K - 1), dtype=torch.float32, device=logits.device)
-        _lib.check(L.du_val_dice_ce(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, K, HW, _p(ws), n, _st()), "du_val_dice_ce")
-        mult = 1.0
-        if group is not None and torch.distributed.is_initialized():
-            _small_all_reduce(sums[1:], group, "dice_sums")
-            mult = float(torch.distributed.get_world_size(group))
-        _lib.check(L.du_dice_ce_finish(_p(sums), _p(loss), _p(coef), K, B * HW, float(smooth), mult, _st()), "du_dice_ce_finish")
+        loss, _ = _loss_forward(
+            logits.device, n, 1 + 3 * (K - 1), 1, 2 * (K - 1), 1, group,
+            lambda ws, sums: _lib.check(L.du_val_dice_ce(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, K, HW, _p(ws), n, _st()),
+                                        "du_val_dice_ce"),
+            _finish_dice_ce(K, B * HW, smooth))
     return loss.view(()), counts
 
 
@@ -2773,13 +2768,11 @@ def val_dice_bce(logits, target, has_ignore, smooth=1e-5, group=None, counts=Non
     if n <= 0:
         raise RuntimeError(f"dinounet_hip: the fused validation pass supports 1..8 regions, got {R}")
     counts = _val_bufs(R, counts, accum, logits.device)
-    ws = torch.empty(n, dtype=torch.float32, device=logits.device)
-    sums = torch.empty(2 + 3 * R, dtype=torch.float32, device=logits.device)
-    _lib.check(L.du_val_dice_bce(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, R, HW, u, _p(ws), n, _st()), "du_val_dice_bce")
-    mult = _dice_group(sums, group, "dice_sums")
-    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-    coef = torch.empty(2 * R + 1, dtype=torch.float32, device=logits.device)
-    _lib.check(L.du_dice_bce_finish(_p(sums), _p(loss), _p(coef), R, u, float(smooth), mult, _st()), "du_dice_bce_finish")
+    loss, _ = _loss_forward(
+        logits.device, n, 2 + 3 * R, 1, 2 * R + 1, 2, group,
+        lambda ws, sums: _lib.check(L.du_val_dice_bce(_p(logits), _p(tgt), _p(sums), _p(counts), _p(accum), B, R, HW, u, _p(ws), n, _st()),
+                                    "du_val_dice_bce"),
+        _finish_dice_bce(R, u, smooth))
     return loss.view(()), counts
 
 

@@ -22,6 +22,11 @@ def _ddp_default(group):
     return dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or _FORCE_SMALL)
 
 
+def _loss_group(ddp, group):
+    """the group argument of a fused loss: the process group its Dice sums are all-reduced over, None for a local loss"""
+    return (group if group is not None else dist.group.WORLD) if ddp else None
+
+
 class _AllReduceSumGrad(torch.autograd.Function):
     """dinounet/utilities/ddp_allgather.py:25-48 followed by .sum(0): all-gather forward / all-reduce backward."""
 
@@ -52,7 +57,7 @@ def dc_and_ce_loss(logits, target, smooth=1e-5, ddp=None, group=None, ignore_lab
         from . import ops
         if ddp is None:
             ddp = _ddp_default(group)
-        return ops.dice_ce_loss(logits, target, smooth, (group if group is not None else dist.group.WORLD) if ddp else None)
+        return ops.dice_ce_loss(logits, target, smooth, _loss_group(ddp, group))
     lab = target[:, 0].long()
     ce = F.cross_entropy(logits, lab)
     prob = torch.softmax(logits, 1)
@@ -95,8 +100,7 @@ def _dc_and_ce_masked(logits, target, ignore_label, smooth=1e-5, ddp=None, group
         from . import ops
         if ddp is None:
             ddp = _ddp_default(group)
-        return ops.dice_ce_masked_loss(logits, target, ignore_label, smooth,
-                                       (group if group is not None else dist.group.WORLD) if ddp else None)
+        return ops.dice_ce_masked_loss(logits, target, ignore_label, smooth, _loss_group(ddp, group))
     lab = target[:, 0].long()
     m = lab != ignore_label
     lab0 = torch.where(m, lab, torch.zeros_like(lab))
@@ -190,7 +194,7 @@ def dc_and_topk_loss(logits, target, k=10, smooth=1e-5, ddp=None, group=None, ig
         ddp = _ddp_default(group)
     if _topk_fused(logits):
         from . import ops
-        return ops.dice_topk_loss(logits, target, k, ignore_label, smooth, (group if group is not None else dist.group.WORLD) if ddp else None)
+        return ops.dice_topk_loss(logits, target, k, ignore_label, smooth, _loss_group(ddp, group))
     return _topk_ce_torch(logits, target, k, ignore_label) - _soft_dice_torch(logits, target, ignore_label, smooth, ddp, group)
 
 
@@ -211,7 +215,7 @@ def dc_and_bce_loss(logits, target, use_ignore_label=False, smooth=1e-5, ddp=Non
     if logits.is_cuda and 1 <= R <= 8:
         from . import ops
         tgt = target if target.dtype == torch.uint8 else target.to(torch.uint8)
-        return ops.dice_bce_loss(logits, tgt, u, smooth, (group if group is not None else dist.group.WORLD) if ddp else None)
+        return ops.dice_bce_loss(logits, tgt, u, smooth, _loss_group(ddp, group))
     y = target[:, :R].to(logits.dtype)
     bce = F.binary_cross_entropy_with_logits(logits, y, reduction="none")
     x = torch.sigmoid(logits)
@@ -433,7 +437,7 @@ class DeepSupervisionLoss(torch.nn.Module):
                 raise RuntimeError(f"DeepSupervisionLoss: region table lives on {table.device}, target on {target.device} "
                                    "(move the module with .to())")
         return ops.ds_seg_loss(outs, target, self.mode, self.weights, table=table, ignore_label=self.ignore_label, smooth=self.smooth,
-                               group=(self.group if self.group is not None else dist.group.WORLD) if ddp else None,
+                               group=_loss_group(ddp, self.group),
                                return_scale_losses=return_scale_losses)
 
 
@@ -753,7 +757,7 @@ def _val_loss_counts(logits, target, mode, regions, ignore_label, table, smooth,
         ddp = _ddp_default(group)
     if fused:
         from . import ops
-        g = (group if group is not None else dist.group.WORLD) if ddp else None
+        g = _loss_group(ddp, group)
         if mode == "regions":
             onehot = labels_to_regions(target, regions, ignore_label, table=table)
             return ops.val_dice_bce(logits, onehot, ignore_label is not None, smooth, g, counts, accum)
