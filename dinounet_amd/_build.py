@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdinounet_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_glds.hip", "gemm_p8.hip", "gemm_rk.hip", "gemm_skinny.hip", "conv_halo.hip", "conv_strip.hip", "attention.hip", "norm.hip", "norm_gemm.hip", "msda.hip", "elementwise.hip", "dwconv.hip", "loss.hip", "loss_topk.hip", "optim.hip", "augment.hip", "augment_spline.hip", "export.hip", "ensemble.hip", "surface.hip", "cc.hip", "preprocess.hip", "dataload.hip", "fingerprint.hip", "window.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_glds.hip", "gemm_p8.hip", "gemm_rk.hip", "gemm_skinny.hip", "conv_halo.hip", "conv_strip.hip", "attention.hip", "norm.hip", "norm_gemm.hip", "msda.hip", "elementwise.hip", "dwconv.hip", "loss.hip", "loss_topk.hip", "loss_opt.hip", "optim.hip", "augment.hip", "augment_spline.hip", "export.hip", "ensemble.hip", "surface.hip", "cc.hip", "preprocess.hip", "dataload.hip", "fingerprint.hip", "window.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-gpu-rdc"]
 # the measurement tools' build: environment knobs (DU_CONV_STRIP, DU_SKINNY_FUSE_KMAX, ...) compiled in; the release library has none (csrc/common.h)
 if os.environ.get("DINOUNET_DEBUG_KNOBS") == "1":
@@ -20,7 +20,7 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "conv_stri
 # kernels of these files must not use scratch: a register spill in a GEMM / attention / conv main loop or epilogue is a silent multi-ms
 # regression (seen: an address helper inlined into every epilogue put 576 bytes per lane of the 256 x 256 kernel on the stack, +7 ms per
 # step, all tests green).  The build reads hipcc's resource-usage remarks and fails on ScratchSize > 0 there.
-NO_SCRATCH = ("loss.hip", "loss_topk.hip", "gemm_bf16.hip", "gemm_glds.hip", "gemm_p8.hip", "gemm_rk.hip", "gemm_skinny.hip", "conv_halo.hip", "conv_strip.hip", "attention.hip", "norm_gemm.hip", "surface.hip", "dwconv.hip", "cc.hip", "preprocess.hip", "dataload.hip", "fingerprint.hip", "ensemble.hip", "augment_spline.hip", "window.hip")
+NO_SCRATCH = ("loss.hip", "loss_topk.hip", "loss_opt.hip", "gemm_bf16.hip", "gemm_glds.hip", "gemm_p8.hip", "gemm_rk.hip", "gemm_skinny.hip", "conv_halo.hip", "conv_strip.hip", "attention.hip", "norm_gemm.hip", "surface.hip", "dwconv.hip", "cc.hip", "preprocess.hip", "dataload.hip", "fingerprint.hip", "ensemble.hip", "augment_spline.hip", "window.hip")
 REMARK = "-Rpass-analysis=kernel-resource-usage"
 # timing-ablation and cycle-probe instantiations of the attention kernel (tools/attn_ablate.py) may spill: they never run in the product
 import re as _re

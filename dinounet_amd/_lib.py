@@ -48,6 +48,12 @@ class TnJob(C.Structure):
                 ("taps", C.c_int32), ("inner", C.c_int32), ("inner_total", C.c_int32), ("c_off", C.c_int32)]
 
 
+class LossOpt(C.Structure):
+    """du_loss_opt (include/dinounet_hip.h): the options of a fused loss of csrc/loss_opt.hip; passed as C.byref(...)."""
+    _fields_ = [("n", C.c_int), ("regions", C.c_int), ("has_ignore", C.c_int), ("ignore", C.c_int64), ("do_bg", C.c_int),
+                ("batch_dice", C.c_int), ("weight_ce", C.c_float), ("weight_dice", C.c_float), ("class_w", C.c_void_p)]
+
+
 _CTYPE = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "int32_t": C.c_int32, "double": C.c_double}
 
 

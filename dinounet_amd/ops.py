@@ -2596,6 +2596,109 @@ def dice_bce_loss(logits, target, has_ignore, smooth=1e-5, group=None):
     return _DiceBCE.apply(logits, target, bool(has_ignore), smooth, group)
 
 
+def _loss_opt_struct(n, regions, has_ignore, ignore, do_bg, batch_dice, weight_ce, weight_dice, class_w):
+    return _lib.LossOpt(int(n), 1 if regions else 0, 1 if has_ignore else 0, int(ignore), 1 if do_bg else 0, 1 if batch_dice else 0,
+                        float(weight_ce), float(weight_dice), None if class_w is None else class_w.data_ptr())
+
+
+def _loss_opt_forward(ctx, logits, tgt, o, smooth, group, what):
+    """forward of the two option losses (csrc/loss_opt.hip): sums (rows, 2 + 3 CD), the all-reduce of a batch-Dice row's Dice columns
+    (none for per-sample Dice: the reference gathers only under batch_dice, dice.py:106-110), finish -> loss; saves for backward"""
+    import ctypes
+    B, N, H, W = logits.shape
+    HW = H * W
+    L = _lib.lib()
+    ref = ctypes.byref(o)
+    n = int(L.du_loss_opt_ws_elems(ref, B, HW))
+    if n <= 0:
+        raise RuntimeError(f"dinounet_hip: {what}")
+    CD = N if (o.regions or o.do_bg) else N - 1
+    rows = 1 if o.batch_dice else B
+    loss, coef = _loss_forward(
+        logits.device, n, rows * (2 + 3 * CD), 1, rows * 2 * CD + 1, 2, group if o.batch_dice else None,
+        lambda ws, sums: _lib.check(L.du_loss_opt_sums(ref, _p(logits), _p(tgt), _p(sums), B, HW, _p(ws), n, _st()), "du_loss_opt_sums"),
+        lambda sums, loss, coef, mult, ws: _lib.check(
+            L.du_loss_opt_finish(ref, _p(sums), _p(loss), _p(coef), B, float(smooth), mult, _st()), "du_loss_opt_finish"))
+    ctx.opt = o
+    return loss, coef
+
+
+def _loss_opt_backward(ctx, go, logits, tgt, coef):
+    import ctypes
+    B, N, H, W = logits.shape
+    dl = torch.empty_like(logits)
+    gof = go.float().contiguous()
+    _lib.check(_lib.lib().du_loss_opt_bwd(ctypes.byref(ctx.opt), _p(logits), _p(tgt), _p(coef), _p(gof), _p(dl), B, H * W, _st()),
+               "du_loss_opt_bwd")
+    return dl
+
+
+class _DiceCEOpt(torch.autograd.Function):
+    """DC_and_CE_loss with the options of its classes (compound_losses.py:8-56: weight_ce, weight_dice, ignore_label;
+    MemoryEfficientSoftDiceLoss batch_dice, do_bg, dice.py:58-119; RobustCrossEntropyLoss(weight)) on fp32 NCHW logits, fused like
+    _DiceCEMasked (csrc/loss_opt.hip).  class_w: a device tensor of K fp32 weights or None; it is saved for the backward pass."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_label, do_bg, batch_dice, weight_ce, weight_dice, class_w, smooth, group):
+        logits = logits.float().contiguous()
+        B, K, H, W = logits.shape
+        tgt = _labels2d(target, B, H * W)
+        if class_w is not None and (class_w.dtype != torch.float32 or class_w.numel() != K or class_w.device != logits.device):
+            raise RuntimeError(f"dinounet_hip: class weights must be {K} fp32 values on {logits.device}")
+        cw = None if class_w is None else class_w.contiguous()
+        o = _loss_opt_struct(K, False, ignore_label is not None, 0 if ignore_label is None else ignore_label, do_bg, batch_dice, weight_ce,
+                             weight_dice, cw)
+        loss, coef = _loss_opt_forward(ctx, logits, tgt, o, smooth, group,
+                                       f"fused Dice+CE with loss options supports 2..8 classes, got {K}")
+        ctx.save_for_backward(logits, tgt, coef, *(() if cw is None else (cw,)))
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, go):
+        logits, tgt, coef = ctx.saved_tensors[:3]
+        return (_loss_opt_backward(ctx, go, logits, tgt, coef),) + (None,) * 9
+
+
+class _DiceBCEOpt(torch.autograd.Function):
+    """DC_and_BCE_loss with weight_ce, weight_dice and batch_dice (compound_losses.py:59-99, dice.py:58-119) on fp32 NCHW logits and a
+    uint8 one-hot target (B, R + u, H, W), u = 1 with the ignore channel last; fused like _DiceBCE (csrc/loss_opt.hip)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, has_ignore, batch_dice, weight_ce, weight_dice, smooth, group):
+        logits = logits.float().contiguous()
+        B, R, H, W = logits.shape
+        u = 1 if has_ignore else 0
+        if target.dtype != torch.uint8 or tuple(target.shape) != (B, R + u, H, W):
+            raise RuntimeError(f"dinounet_hip: region target must be uint8 {(B, R + u, H, W)}, got {target.dtype} {tuple(target.shape)}")
+        tgt = target.contiguous()
+        o = _loss_opt_struct(R, True, u, 0, True, batch_dice, weight_ce, weight_dice, None)
+        loss, coef = _loss_opt_forward(ctx, logits, tgt, o, smooth, group,
+                                       f"fused Dice+BCE with loss options supports 1..8 regions, got {R}")
+        ctx.save_for_backward(logits, tgt, coef)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, go):
+        logits, tgt, coef = ctx.saved_tensors
+        return (_loss_opt_backward(ctx, go, logits, tgt, coef),) + (None,) * 7
+
+
+def dice_ce_opt_loss(logits, target, ignore_label=None, do_bg=False, batch_dice=True, weight_ce=1.0, weight_dice=1.0, class_w=None,
+                     smooth=1e-5, group=None):
+    """logits (B,K,H,W) fp32, target (B,1,H,W) integer labels in [0,K) or ignore_label -> weight_ce CE - weight_dice mean soft Dice, the
+    CE weighted per class by class_w (device tensor of K fp32, None: 1), Dice over classes 1..K-1 (do_bg: 0..K-1), over the batch or per
+    sample (batch_dice=False: no all-reduce over `group`).  The options are validated by training.build_loss / SegLoss; the library refuses
+    contradictions with DU_ERR_BAD_ARG."""
+    _req(logits, target)
+    return _DiceCEOpt.apply(logits, target, ignore_label, do_bg, batch_dice, weight_ce, weight_dice, class_w, smooth, group)
+
+
+def dice_bce_opt_loss(logits, target, has_ignore, batch_dice=True, weight_ce=1.0, weight_dice=1.0, smooth=1e-5, group=None):
+    """logits (B,R,H,W) fp32, target (B,R+has_ignore,H,W) uint8 {0,1} -> weight_ce BCE - weight_dice mean soft Dice over the regions"""
+    _req(logits, target)
+    return _DiceBCEOpt.apply(logits, target, bool(has_ignore), batch_dice, weight_ce, weight_dice, smooth, group)
+
+
 def labels_to_regions(seg, table, ignore_label=None):
     """seg (B,1,H,W) integer labels, table (R) int64 device bit masks (bit l = label l in region r) -> uint8 (B, R + u, H, W),
     u = 1 with an ignore label (last plane = [seg == ignore_label])."""

@@ -181,7 +181,8 @@ class Trainer:
     """nnUNetTrainer's training loop for one fold of a DeviceDataset (defaults: nnUNetTrainer.py:146-151, 187).
 
     net: the network, already on its device (the trainable parameters are those with requires_grad).  dataset: a DeviceDataset; do_split
-    (fold, splits) selects the training and the validation cases.  The loss is build_loss(num_classes, regions, ignore_label, topk_percent),
+    (fold, splits) selects the training and the validation cases.  The loss is build_loss(num_classes, regions, ignore_label, topk_percent,
+    **loss_options) (loss_options: None or a dict of build_loss's weight_ce, weight_dice, batch_dice, do_bg, ce_class_weights; kept in init_args),
     with deep_supervision wrapped with deep_supervision_weights(number of decoder outputs, world > 1).  The optimiser is FusedClipSGD(initial_lr,
     momentum 0.99, nesterov, weight_decay) on the GPU and torch.optim.SGD with the same numbers on the CPU, unless `optimizer` is given.
     The batches are TrainBatches(val=False) seeded with `seed` (augmentation: seed + 1) and TrainBatches(val=True) seeded with seed + 2,
@@ -196,7 +197,7 @@ class Trainer:
                  all_labels=None, num_epochs=1000, num_iterations_per_epoch=250, num_val_iterations_per_epoch=10, initial_lr=1e-2,
                  weight_decay=3e-5, oversample_foreground_percent=0.33, save_every=50, output_folder=None, seed=None, graph=True,
                  interpolation="keys", use_mask_for_norm=None, deep_supervision=False, topk_percent=None, reducer=None, rank=0, world=1,
-                 train_batches=None, val_batches=None, optimizer=None):
+                 train_batches=None, val_batches=None, optimizer=None, loss_options=None):
         from .dataloading import TrainBatches
         from .training import build_loss, deep_supervision_weights
         self.net, self.dataset = net, dataset
@@ -226,6 +227,16 @@ class Trainer:
                               save_every=self.save_every, seed=seed, graph=bool(graph), interpolation=interpolation,
                               use_mask_for_norm=use_mask_for_norm, deep_supervision=bool(deep_supervision), topk_percent=topk_percent,
                               world=self.world)
+        # the options of the reference's loss classes (build_loss: weight_ce, weight_dice, batch_dice, do_bg, ce_class_weights) as plain
+        # Python values; None leaves init_args, and so the checkpoint, without the key
+        self.loss_options = None
+        if loss_options is not None:
+            unknown = set(loss_options) - {"weight_ce", "weight_dice", "batch_dice", "do_bg", "ce_class_weights"}
+            if unknown:
+                raise ValueError(f"loss_options: unknown keys {sorted(unknown)}")
+            self.loss_options = {k: ([float(w) for w in v] if k == "ce_class_weights" and v is not None else v)
+                                 for k, v in loss_options.items()}
+            self.init_args["loss_options"] = self.loss_options
         if seed is not None:
             # the default generator of the trainer's device alone (the steps draw from it): no other generator of the process is touched
             if self.device.type == "cuda":
@@ -242,7 +253,7 @@ class Trainer:
                 raise ValueError("deep_supervision: the number of outputs is read from net.decoder.seg_layers, which this network lacks")
             ds_weights = deep_supervision_weights(len(heads), ddp=self.world > 1)
         self.loss = build_loss(self.num_classes, regions=regions, ignore_label=ignore_label, ddp=True if self.world > 1 else None,
-                               group=None, deep_supervision_weights=ds_weights, topk_percent=topk_percent)
+                               group=None, deep_supervision_weights=ds_weights, topk_percent=topk_percent, **(self.loss_options or {}))
         self.params = [p for p in net.parameters() if p.requires_grad]
         if optimizer is not None:
             self.optimizer = optimizer

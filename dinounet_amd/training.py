@@ -44,12 +44,132 @@ class _AllReduceSumGrad(torch.autograd.Function):
         return g, None
 
 
-def dc_and_ce_loss(logits, target, smooth=1e-5, ddp=None, group=None, ignore_label=None):
+def check_loss_options(num_classes, regions=None, topk_percent=None, weight_ce=1.0, weight_dice=1.0, batch_dice=True, do_bg=None,
+                       ce_class_weights=None):
+    """The options of the reference's loss classes that the trainer freezes (DC_and_CE_loss / DC_and_BCE_loss weight_ce, weight_dice;
+    MemoryEfficientSoftDiceLoss batch_dice, do_bg; ce_kwargs={'weight': w}), validated on the host -> (weight_ce, weight_dice,
+    batch_dice, do_bg, class weights as a tuple or None, options_default).  do_bg None is the trainer's choice: False for softmax,
+    True for regions.  ValueError for: both weights 0; a negative or non-finite weight; a class weight <= 0 or not finite, or not
+    num_classes of them; ce_class_weights or do_bg=False together with regions; any non-default option together with topk_percent."""
+    import math
+    for name, v in (("weight_ce", weight_ce), ("weight_dice", weight_dice)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    weight_ce, weight_dice = float(weight_ce), float(weight_dice)
+    if weight_ce == 0.0 and weight_dice == 0.0:
+        raise ValueError("weight_ce and weight_dice are both 0: no loss is left")
+    if not isinstance(batch_dice, bool):
+        raise ValueError(f"batch_dice must be a bool, got {batch_dice!r}")
+    if do_bg is not None and not isinstance(do_bg, bool):
+        raise ValueError(f"do_bg must be None or a bool, got {do_bg!r}")
+    cw = None
+    if ce_class_weights is not None:
+        cw = tuple(float(v) for v in (ce_class_weights.tolist() if isinstance(ce_class_weights, torch.Tensor) else ce_class_weights))
+        if regions is not None:
+            raise ValueError("ce_class_weights with regions: BCEWithLogitsLoss has no class weights (pos_weight is out of scope)")
+        if len(cw) != num_classes:
+            raise ValueError(f"ce_class_weights: {len(cw)} weights for {num_classes} classes")
+        if not all(math.isfinite(v) and v > 0 for v in cw):
+            raise ValueError(f"ce_class_weights must be positive finite numbers, got {cw!r}")
+    if regions is not None and do_bg is False:
+        raise ValueError("do_bg=False with regions: every region is a foreground structure (the reference uses do_bg=True there)")
+    bg = (regions is not None) if do_bg is None else do_bg
+    default = (weight_ce == 1.0 and weight_dice == 1.0 and batch_dice and cw is None and bg == (regions is not None))
+    if topk_percent is not None and not default:
+        raise ValueError("loss options (weight_ce, weight_dice, batch_dice, do_bg, ce_class_weights) are not available together with "
+                         "topk_percent: the top-k family stays at the trainer's defaults")
+    return weight_ce, weight_dice, batch_dice, bg, cw, default
+
+
+def _dice_term(inter, sum_pred, sum_gt, smooth, batch_dice, ddp, group):
+    """MemoryEfficientSoftDiceLoss's mean Dice from per-(sample, class) sums (B, C), dice.py:106-118: batch_dice adds over the batch
+    (globally under DDP), otherwise dc stays (B, C), nothing is gathered, and the mean runs over both axes"""
+    if batch_dice:
+        return _global_dice(inter, sum_pred, sum_gt, smooth, ddp, group)
+    return ((2 * inter + smooth) / torch.clip(sum_gt + sum_pred + smooth, 1e-8)).mean()
+
+
+def _dc_and_ce_opt_torch(logits, target, ignore_label, smooth, ddp, group, weight_ce, weight_dice, batch_dice, do_bg, class_w):
+    """DC_and_CE_loss with every option, in torch: the CPU / many-class path and, in fp64, the oracle of csrc/loss_opt.hip.
+    CE = sum_valid w_t nll / sum_valid w_t (F.cross_entropy(weight=w, ignore_index) = torch's weighted mean), exactly 0 when the
+    denominator is 0, decided without a host read; a term whose weight is 0 is not computed (compound_losses.py:50-55)."""
+    lab = target[:, 0].long()
+    m = (lab != ignore_label) if ignore_label is not None else torch.ones_like(lab, dtype=torch.bool)
+    lab0 = torch.where(m, lab, torch.zeros_like(lab))
+    mf = m[:, None].to(logits.dtype)
+    total = None
+    if weight_ce != 0:
+        nll = -torch.log_softmax(logits, 1).gather(1, lab0[:, None])
+        wt = mf if class_w is None else class_w.to(logits.dtype)[lab0][:, None] * mf
+        den = wt.sum()
+        total = weight_ce * ((nll * wt).sum() / torch.where(den > 0, den, torch.ones_like(den)))
+    if weight_dice != 0:
+        c0 = 0 if do_bg else 1
+        prob = torch.softmax(logits, 1)
+        with torch.no_grad():
+            onehot = torch.zeros(prob.shape, device=prob.device, dtype=prob.dtype).scatter_(1, lab0[:, None], 1)[:, c0:] * mf
+            sum_gt = onehot.sum((2, 3))
+        p = prob[:, c0:] * mf
+        dc = weight_dice * _dice_term((p * onehot).sum((2, 3)), p.sum((2, 3)), sum_gt, smooth, batch_dice, ddp, group)
+        total = -dc if total is None else total - dc
+    return total
+
+
+def _dc_and_bce_opt_torch(logits, target, u, smooth, ddp, group, weight_ce, weight_dice, batch_dice):
+    """DC_and_BCE_loss with weight_ce, weight_dice and batch_dice, in torch (CPU path and fp64 oracle); target (B, R + u, H, W)"""
+    R = logits.shape[1]
+    y = target[:, :R].to(logits.dtype)
+    mf = (1 - target[:, -1:]).bool().to(logits.dtype) if u else None
+    total = None
+    if weight_ce != 0:
+        bce = F.binary_cross_entropy_with_logits(logits, y, reduction="none")
+        total = weight_ce * ((bce * mf).sum() / torch.clip(mf.sum(), min=1e-8) if u else bce.mean())
+    if weight_dice != 0:
+        x = torch.sigmoid(logits)
+        if u:
+            y, x = y * mf, x * mf
+        dc = weight_dice * _dice_term((x * y).sum((2, 3)), x.sum((2, 3)), y.sum((2, 3)), smooth, batch_dice, ddp, group)
+        total = -dc if total is None else total - dc
+    return total
+
+
+def _class_w_tensor(ce_class_weights, device, dtype=torch.float32):
+    """the class weights as a tensor: fp32 for the kernels, the logits' dtype for the torch formula"""
+    if ce_class_weights is None:
+        return None
+    if isinstance(ce_class_weights, torch.Tensor):
+        return ce_class_weights.to(device=device, dtype=dtype)
+    return torch.tensor([float(v) for v in ce_class_weights], dtype=dtype, device=device)
+
+
+def dc_and_ce_loss(logits, target, smooth=1e-5, ddp=None, group=None, ignore_label=None, weight_ce=1.0, weight_dice=1.0, batch_dice=True,
+                   do_bg=None, ce_class_weights=None):
     """DC_and_CE_loss (compound_losses.py:8-56) with MemoryEfficientSoftDiceLoss(batch_dice=True, do_bg=False,
     smooth=1e-5) (dice.py:58-119, trainer config nnUNetTrainer.py:363-365).  target (B,1,H,W) integer labels.
     On the GPU (2..8 classes) this is the fused HIP loss (ops.dice_ce_loss); the torch formula below is the CPU / many-class path
     used by the gloo tests.  With `ignore_label` the pixels carrying it are masked out (compound_losses.py:38-53): see
-    _dc_and_ce_masked."""
+    _dc_and_ce_masked.
+    weight_ce, weight_dice, batch_dice, do_bg and ce_class_weights (K weights, a sequence or a tensor) are the options of the reference's
+    classes (check_loss_options); at their defaults the code below runs as before, otherwise the fused option loss
+    (ops.dice_ce_opt_loss, csrc/loss_opt.hip) on the GPU and _dc_and_ce_opt_torch elsewhere."""
+    weight_ce, weight_dice, batch_dice, do_bg, cw, default = check_loss_options(
+        logits.shape[1], None, None, weight_ce, weight_dice, batch_dice, do_bg,
+        None if isinstance(ce_class_weights, torch.Tensor) else ce_class_weights)
+    if isinstance(ce_class_weights, torch.Tensor):        # a prepared device tensor (SegLoss validated its values): no read-back here
+        if ce_class_weights.numel() != logits.shape[1]:
+            raise ValueError(f"ce_class_weights: {ce_class_weights.numel()} weights for {logits.shape[1]} classes")
+        default = False
+    if not default:
+        K = logits.shape[1]
+        if ddp is None:
+            ddp = _ddp_default(group)
+        if logits.is_cuda and 2 <= K <= 8:
+            from . import ops
+            class_w = _class_w_tensor(ce_class_weights, logits.device)
+            return ops.dice_ce_opt_loss(logits, target, ignore_label, do_bg, batch_dice, weight_ce, weight_dice, class_w, smooth,
+                                        _loss_group(ddp, group))
+        class_w = _class_w_tensor(ce_class_weights, logits.device, logits.dtype)
+        return _dc_and_ce_opt_torch(logits, target, ignore_label, smooth, ddp, group, weight_ce, weight_dice, batch_dice, do_bg, class_w)
     if ignore_label is not None:
         return _dc_and_ce_masked(logits, target, ignore_label, smooth, ddp, group)
     K = logits.shape[1]
@@ -198,13 +318,16 @@ def dc_and_topk_loss(logits, target, k=10, smooth=1e-5, ddp=None, group=None, ig
     return _topk_ce_torch(logits, target, k, ignore_label) - _soft_dice_torch(logits, target, ignore_label, smooth, ddp, group)
 
 
-def dc_and_bce_loss(logits, target, use_ignore_label=False, smooth=1e-5, ddp=None, group=None):
+def dc_and_bce_loss(logits, target, use_ignore_label=False, smooth=1e-5, ddp=None, group=None, weight_ce=1.0, weight_dice=1.0,
+                    batch_dice=True):
     """DC_and_BCE_loss (compound_losses.py:59-99) with MemoryEfficientSoftDiceLoss(sigmoid, batch_dice=True, do_bg=True, smooth=1e-5)
     (nnUNetTrainer.py:356-361): region-based training.  logits (B,R,H,W); target the reference's one-hot form (B, R + u, H, W) in {0,1},
     u = 1 with `use_ignore_label` (ignore channel last, m = 1 - target[:, -1]).  BCE is the mean over every element without an ignore
     channel, else sum(bce m) / clip(sum m, 1e-8) with the (B,1,H,W) mask broadcast over R -- the denominator counts pixels (:95).
     On the GPU (1..8 regions) the fused HIP loss (ops.dice_bce_loss; a non-uint8 target is converted once); the torch formula below is
-    the CPU path.  Soft (non-binary) targets are outside this contract."""
+    the CPU path.  Soft (non-binary) targets are outside this contract.
+    weight_ce, weight_dice and batch_dice are the options of the reference's classes (check_loss_options): at their defaults the code
+    below runs as before, otherwise ops.dice_bce_opt_loss (csrc/loss_opt.hip) on the GPU and _dc_and_bce_opt_torch elsewhere."""
     R = logits.shape[1]
     u = 1 if use_ignore_label else 0
     if target.shape[1] != R + u:
@@ -212,6 +335,13 @@ def dc_and_bce_loss(logits, target, use_ignore_label=False, smooth=1e-5, ddp=Non
                          f"{' + the ignore channel' if u else ''})")
     if ddp is None:
         ddp = _ddp_default(group)
+    weight_ce, weight_dice, batch_dice, _, _, default = check_loss_options(R, (), None, weight_ce, weight_dice, batch_dice)
+    if not default:
+        if logits.is_cuda and 1 <= R <= 8:
+            from . import ops
+            tgt = target if target.dtype == torch.uint8 else target.to(torch.uint8)
+            return ops.dice_bce_opt_loss(logits, tgt, u, batch_dice, weight_ce, weight_dice, smooth, _loss_group(ddp, group))
+        return _dc_and_bce_opt_torch(logits, target, u, smooth, ddp, group, weight_ce, weight_dice, batch_dice)
     if logits.is_cuda and 1 <= R <= 8:
         from . import ops
         tgt = target if target.dtype == torch.uint8 else target.to(torch.uint8)
@@ -274,10 +404,17 @@ class SegLoss(torch.nn.Module):
     labels or with an ignore label) or DC_and_BCE_loss (regions, with or without an ignore label); with `topk_percent` DC_and_topk_loss
     (compound_losses.py:102-150, modes "topk" / "topk_ignore"; not with regions).  Called as loss(logits, target) with
     integer label maps (B,1,H,W) in both modes; in region mode the labels become the one-hot region target on the device inside the same
-    step (labels_to_regions with the table built here, at construction, outside any capture)."""
+    step (labels_to_regions with the table built here, at construction, outside any capture).
+    weight_ce, weight_dice, batch_dice, do_bg and ce_class_weights are the options of the reference's classes (check_loss_options has
+    their meaning and the ValueErrors); `options_default` tells whether all of them are at the trainer's values, and then forward is the
+    code path it has always been.  Otherwise the fused option losses of csrc/loss_opt.hip run on the GPU (the class weights live in the
+    buffer `class_w`, built here).  The top-k family takes no options."""
 
-    def __init__(self, num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None, topk_percent=None):
+    def __init__(self, num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None, topk_percent=None,
+                 weight_ce=1.0, weight_dice=1.0, batch_dice=True, do_bg=None, ce_class_weights=None):
         super().__init__()
+        (self.weight_ce, self.weight_dice, self.batch_dice, self.do_bg, self.ce_class_weights, self.options_default) = check_loss_options(
+            num_classes, regions, topk_percent, weight_ce, weight_dice, batch_dice, do_bg, ce_class_weights)
         if topk_percent is not None:
             if regions is not None:
                 raise ValueError("top-k loss with regions: the reference has no such loss (DC_and_topk_loss is softmax-only)")
@@ -303,8 +440,31 @@ class SegLoss(torch.nn.Module):
         self.mode = "regions" if self.regions is not None else ("softmax_ignore" if ignore_label is not None else "softmax")
         if topk_percent is not None:
             self.mode = "topk_ignore" if ignore_label is not None else "topk"
+        if self.ce_class_weights is not None:
+            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+            self.register_buffer("class_w", _class_w_tensor(self.ce_class_weights, dev), persistent=False)
+
+    def _forward_options(self, logits, target):
+        """the loss with non-default options: the functions above with the options of this module"""
+        if self.regions is None:
+            cw = None
+            if self.ce_class_weights is not None:
+                cw = self.class_w if logits.is_cuda else self.ce_class_weights     # (the torch formula takes them in the logits' dtype)
+                if logits.is_cuda and cw.device != logits.device:
+                    raise RuntimeError(f"SegLoss: class weights live on {cw.device}, logits on {logits.device} (move the module with .to())")
+            return dc_and_ce_loss(logits, target, self.smooth, ddp=self.ddp, group=self.group, ignore_label=self.ignore_label,
+                                  weight_ce=self.weight_ce, weight_dice=self.weight_dice, batch_dice=self.batch_dice, do_bg=self.do_bg,
+                                  ce_class_weights=cw)
+        table = self.table if self.table.device == target.device else None
+        if target.is_cuda and table is None:
+            raise RuntimeError(f"SegLoss: region table lives on {self.table.device}, target on {target.device} (move the module with .to())")
+        onehot = labels_to_regions(target, self.regions, self.ignore_label, table=table)
+        return dc_and_bce_loss(logits, onehot, self.ignore_label is not None, self.smooth, ddp=self.ddp, group=self.group,
+                               weight_ce=self.weight_ce, weight_dice=self.weight_dice, batch_dice=self.batch_dice)
 
     def forward(self, logits, target):
+        if not self.options_default:
+            return self._forward_options(logits, target)
         if self.topk_percent is not None:
             return dc_and_topk_loss(logits, target, self.topk_percent, self.smooth, ddp=self.ddp, group=self.group,
                                     ignore_label=self.ignore_label)
@@ -408,6 +568,8 @@ class DeepSupervisionLoss(torch.nn.Module):
         C_ = outs[0].shape[1]
         if self.mode in ("topk", "topk_ignore"):       # composed of the fused per-scale top-k losses: every scale has its own N and k_vox
             return False
+        if not self.base.options_default:              # composed of the fused per-scale option losses (csrc/loss_opt.hip)
+            return False
         return (all(o.is_cuda for o in outs) and len(outs) <= self.MAX_FUSED_SCALES
                 and ((1 <= C_ <= 8) if self.mode == "regions" else (2 <= C_ <= 8)))
 
@@ -442,15 +604,23 @@ class DeepSupervisionLoss(torch.nn.Module):
 
 
 def build_loss(num_classes, regions=None, ignore_label=None, smooth=1e-5, ddp=None, group=None, deep_supervision_weights=None,
-               topk_percent=None):
+               topk_percent=None, weight_ce=1.0, weight_dice=1.0, batch_dice=True, do_bg=None, ce_class_weights=None):
     """nnUNetTrainer._build_loss (nnUNetTrainer.py:355-387) for this package: the loss module for plain labels, labels with an ignore
     label, or regions (each an int or a tuple of ints; num_classes = number of network outputs = len(regions)).  Validated on the host:
     ValueError for an ignore label below num_classes, more than 8 regions, a region label outside 0..63 or an ignore label inside a
     region.  With `deep_supervision_weights` (one per decoder output, e.g. deep_supervision_weights(3)) the module is wrapped in a
     DeepSupervisionLoss, called as loss(outs, target) on the decoder's list.  With `topk_percent` (e.g. 10) the module is
     DC_and_topk_loss instead of DC_and_CE_loss ("Dice + TopK10"; ValueError together with regions); under deep supervision the wrapper
-    then composes the fused per-scale losses on indexed targets.  Pass the result to TrainStep(loss=...)."""
-    base = SegLoss(num_classes, regions=regions, ignore_label=ignore_label, smooth=smooth, ddp=ddp, group=group, topk_percent=topk_percent)
+    then composes the fused per-scale losses on indexed targets.  Pass the result to TrainStep(loss=...).
+    The options of the reference's loss classes, which its trainer variants set (all validated by check_loss_options, ValueError):
+    weight_ce / weight_dice (1.0; 0 removes the term, value and gradient; not both 0), batch_dice (True; False: per-sample Dice, the mean
+    over (b, c), no all-reduce under DDP), do_bg (None = the trainer's choice: False for softmax, True for regions; True gives class 0 a
+    Dice term; False with regions is refused), ce_class_weights (None; K positive weights: CE = sum w_t nll / sum w_t over the valid
+    pixels, exactly 0 when none is valid; softmax only).  At their defaults the module is exactly the one described above; otherwise the
+    fused option losses (csrc/loss_opt.hip) run on the GPU for 2..8 classes / 1..8 regions and the wrapper composes the per-scale losses.
+    The top-k family stays as it is: any non-default option together with topk_percent is a ValueError."""
+    base = SegLoss(num_classes, regions=regions, ignore_label=ignore_label, smooth=smooth, ddp=ddp, group=group, topk_percent=topk_percent,
+                   weight_ce=weight_ce, weight_dice=weight_dice, batch_dice=batch_dice, do_bg=do_bg, ce_class_weights=ce_class_weights)
     if deep_supervision_weights is None:
         return base
     return DeepSupervisionLoss(base, deep_supervision_weights)
@@ -809,7 +979,7 @@ class ValStep:
     DeepSupervisionLoss and a network that returns a list, the step loss is the module's multi-scale forward value (validation_step :963)
     while the counts come from outs[0] and the full-resolution target (:966-968); with any other loss a list is reduced to outs[0].  With a
     top-k loss (build_loss(..., topk_percent=...)) the counts come from the same softmax / softmax-ignore counts pass and the step loss is
-    the top-k module's forward value.  With a
+    the top-k module's forward value; a loss with non-default options (weight_ce, batch_dice, ...) is arranged the same way.  With a
     group the Dice sums are all-reduced as in the training forward (the reference's validation loss is the same module); under a
     capture that all-reduce is recorded into the graph, a capture that fails falls back to eager steps with a warning, and the multi-rank
     capture itself has been run on CPU / gloo eager steps only, not on several GPUs."""
@@ -828,6 +998,11 @@ class ValStep:
         self.topk_loss = None
         if self.mode in ("topk", "topk_ignore"):
             self.topk_loss = loss.base if isinstance(loss, DeepSupervisionLoss) else loss
+        # a loss with non-default options: the same arrangement (counts from the default counts pass, step loss = the module's value)
+        self.opt_loss = None
+        base = loss.base if isinstance(loss, DeepSupervisionLoss) else loss
+        if base is not None and not getattr(base, "options_default", True):
+            self.opt_loss = base
         self.table = None
         if self.regions is not None and device.type == "cuda":
             self.table = loss.table if loss.table.device == device else _region_table(self.regions, device)
@@ -864,6 +1039,8 @@ class ValStep:
                     loss = ds_loss
                 elif self.topk_loss is not None:
                     loss = self.topk_loss(logits, self.tgt).detach()
+                elif self.opt_loss is not None:
+                    loss = self.opt_loss(logits, self.tgt).detach()
                 self.loss_sum += loss.double()
         finally:
             self.net.train(was_training)

@@ -519,6 +519,37 @@ int du_dice_bce_bwd(const float* logits, const uint8_t* target, const float* coe
 int du_labels_to_regions(const int64_t* seg, const int64_t* table, uint8_t* out, int B, int R, int64_t HW, int has_ignore,
                          int64_t ignore_label, void* stream);
 
+/* ---- the trainer losses with the options of the reference's loss classes (csrc/loss_opt.hip): weight_ce / weight_dice
+        (compound_losses.py:8-99), batch_dice / do_bg (MemoryEfficientSoftDiceLoss, dice.py:58-119), class weights of the CE
+        (RobustCrossEntropyLoss = nn.CrossEntropyLoss(weight)).  The defaults keep the entry points above. ---- */
+typedef struct {
+  int n;               /* K classes in [2,8] (softmax) or R regions in [1,8] (DU_ERR_UNSUPPORTED otherwise) */
+  int regions;         /* 0: softmax, target (B,H*W) int64 labels; 1: sigmoid, target (B,R+has_ignore,H*W) uint8, ignore plane last */
+  int has_ignore;      /* 0 / 1 */
+  int64_t ignore;      /* the ignore label of a softmax target (read with has_ignore) */
+  int do_bg;           /* softmax: class 0 has a Dice term; regions: must be 1 */
+  int batch_dice;      /* 1: Dice sums over the batch (one row); 0: one row per image, the mean runs over (B, classes) */
+  float weight_ce;     /* >= 0, finite, not both 0; a weight of 0 removes the term from the loss and from the gradient */
+  float weight_dice;
+  const float* class_w; /* DEVICE, n floats > 0, or NULL; softmax only: CE = sum w_t nll / sum w_t over the valid pixels */
+} du_loss_opt;
+/* A contradiction in `o` (a flag outside 0 / 1, a negative or non-finite weight, both weights 0, class_w or do_bg = 0 with regions), a
+   null pointer or B, HW <= 0: DU_ERR_BAD_ARG before any launch.  CD = Dice classes = n - 1, n with do_bg, n for regions; rows = 1 with
+   batch_dice, else B.  sums: (rows, 2 + 3 CD) floats = per row [sum w_t nll or sum m bce, sum w_t or n_valid, (I_c, P_c, G_c) c < CD];
+   with rows = B the CE columns of the rows are added in the finish.  scratch: du_loss_opt_ws_elems floats (0: unsupported).  Under data
+   parallelism the caller all-reduces sums[2:] of a batch_dice row and nothing otherwise.  du_loss_opt_finish: loss (1 float) =
+   weight_ce CE - weight_dice mean Dice; coef (rows 2 CD + 1 floats) = [rows][(ca_c, cb_c) c < CD] with weight_dice / (CD rows) and
+   grad_mult folded in, then weight_ce times the CE scale (0 when nothing is valid); a weight of 0 gives exact zeros.
+   du_loss_opt_bwd: dlogits = grad_out[0] * d loss / d logits, exactly 0 in every channel of an ignored pixel.  Two-stage sums in an
+   order that depends on the shape only, no float atomics: bit-reproducible. */
+int64_t du_loss_opt_ws_elems(const du_loss_opt* o, int B, int64_t HW);
+int du_loss_opt_sums(const du_loss_opt* o, const float* logits, const void* target, float* sums, int B, int64_t HW, float* ws,
+                     int64_t ws_elems, void* stream);
+int du_loss_opt_finish(const du_loss_opt* o, const float* sums, float* loss, float* coef, int B, float smooth, float grad_mult,
+                       void* stream);
+int du_loss_opt_bwd(const du_loss_opt* o, const float* logits, const void* target, const float* coef, const float* grad_out,
+                    float* dlogits, int B, int64_t HW, void* stream);
+
 /* ---- deep supervision: DeepSupervisionWrapper (training/loss/deep_supervision.py) around the three losses above, with the targets of
         DownsampleSegForDSTransform2 (custom_transforms/deep_supervision_donwsampling.py) gathered in the kernels ----
    total = sum over the scales with weights[s] != 0, in scale order, of weights[s] * loss_s.  logits / dlogits: HOST arrays of S DEVICE
